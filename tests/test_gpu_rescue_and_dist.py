@@ -119,15 +119,41 @@ def test_config5_hypotheses_against_the_oracle(gpu, orc):  # noqa: F811
     assert cnt[~clean].max() < n_inl - 5
 
 
-def _run_bench(extra, timeout=420):
+def _run_bench(extra, timeout=420, full=True):
+    """the tests below check the legs beside the headline (exchange cost and check, other precision, RANSAC frame): --full"""
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--pmc", "off",
-                        "--no-overlap"] + extra, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1"] +
+                       (["--full", "--no-cpu-baseline", "--pmc", "off", "--no-overlap"] if full else []) + extra,
+                       cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
     assert p.returncode == 0, p.stderr[-2000:]
     assert len(lines) == 1, lines  # the contract: ONE JSON line on stdout
     return json.loads(lines[0])
+
+
+def test_bench_plain_line_and_dumped_outputs(gpu, tmp_path):  # noqa: F811
+    """python bench.py without --full: the headline only, none of the legs beside it; --dump-outputs writes the last timed step's outputs,
+    which are what the library computes for the same seeded inputs in the same (all-float64) mode"""
+    from cvxpnpl_amd import synth
+
+    out = _run_bench(["--dump-outputs", str(tmp_path)], full=False)
+    assert out["metric"].startswith("poses/sec") and out["unit"] == "poses/s" and out["higher_is_better"] is True and out["dtype"] == "f64"
+    assert out["steps"] == 3 and abs(out["value"] * out["ms_per_step"] * 1e-3 - 10000) < 1e-6 * 10000
+    for k in ("mixed", "value_mixed", "median_ms_per_step", "transfer_inclusive", "overlapped", "graph_replay", "latency_b1_us", "cpu_baseline",
+              "cpu_baseline_reference_path_port"):
+        assert k not in out, k
+    assert out["roofline"]["traffic"] is None and "valu" not in out["roofline"]
+    dump = {k: np.load(tmp_path / f"{k}.npy") for k in ("R", "t", "status", "iters", "cost", "work")}
+    assert all(a.dtype == np.float64 for a in dump.values())
+    assert dump["R"].shape == (10000, 3, 3) and dump["t"].shape == (10000, 3) and dump["cost"].shape == (10000, 2)
+    assert np.bincount(dump["status"].astype(int), minlength=5).tolist() == out["solver"]["status_hist"]
+    d = synth.make_pnpl(10000, 10, 0, 2.0, seed=42)
+    r = _solve(gpu, d, 10, 0, f32_sweeps_until=0)
+    assert np.array_equal(dump["status"], r["status"].astype(np.float64))
+    cert = r["status"] == 0
+    assert cert.mean() > 0.999 and synth.geodesic(dump["R"][cert], r["R"][cert]).max() < 1e-9
+    assert np.abs(dump["t"][cert] - r["t"][cert]).max() < 1e-9
 
 
 def test_bench_one_rank_rccl_group(gpu):  # noqa: F811

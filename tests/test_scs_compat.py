@@ -7,7 +7,6 @@ reference itself produced (g3_*_c, e2e_*_c of both golden files) through the sea
 reference's post-processing -- restated in the oracle -- recovers from the returned `x` with what the reference returned.
 """
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -82,25 +81,29 @@ def test_foreign_problem_data_is_refused(golden, grc):
         sc.solve(good, CONES, epsilon=1e-9)
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/cvxpnpl.py"), reason="the reference tree only exists in the build container")
-def test_reference_imports_over_the_seam_and_its_data_is_accepted():
-    """sys.modules['scs'] = cvxpnpl_amd.scs_compat: the unmodified reference imports, picks the SCS-3 names from __version__, and the
-    static data it would pass on every call is the data the seam accepts"""
-    import subprocess
+def test_reference_imports_over_the_seam_and_its_data_is_accepted(golden):
+    """sys.modules['scs'] = cvxpnpl_amd.scs_compat: at import the reference picks its cone key and tolerance keyword from scs.__version__
+    (cvxpnpl.py:11-17; what it picks for each version is recorded in tests/golden/reference_scs_settings.json).  The seam's version picks
+    the SCS-3 names, every keyword the reference then passes is one the seam knows, and the static data it would pass on every call
+    (its _A, _b: g4_A, g4_b) is the data the seam accepts under those cones"""
+    import json
 
-    code = (
-        "import sys; sys.dont_write_bytecode = True; sys.path.insert(0, %r)\n"
-        "import cvxpnpl_amd.scs_compat as sc\n"
-        "sys.modules['scs'] = sc\n"
-        "sys.path.insert(0, '/root/reference')\n"
-        "import cvxpnpl\n"
-        "assert cvxpnpl._CONES == {'z': 22, 'l': 0, 'q': [], 'ep': 0, 's': [10]} or 'z' in cvxpnpl._CONES\n"
-        "assert sc._identify({'A': cvxpnpl._A, 'b': cvxpnpl._b}, cvxpnpl._CONES) == 0\n"
-        "assert cvxpnpl._scs_kwarg_map['eps'] == 'eps_abs'\n"
-        "print('ok')\n" % ROOT
-    )
-    out = subprocess.run([sys.executable, "-B", "-c", code], capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr[-2000:]
+    from packaging import version
+
+    from cvxpnpl_amd import _lib, scs_compat as sc
+
+    with open(os.path.join(ROOT, "tests", "golden", "reference_scs_settings.json")) as f:
+        rec = json.load(f)["by_scs_version"]
+    mine = version.parse(sc.__version__)
+    # the reference's choice for the seam's version: that of the nearest recorded version not above it, and every recorded version
+    # between the first SCS-3 release and it agrees
+    nearest = max((v for v in rec if version.parse(v) <= mine), key=version.parse)
+    picked = rec[nearest]
+    assert all(rec[v] == picked for v in rec if version.parse("3.0.0") <= version.parse(v) <= mine)
+    assert rec["2.999"]["cones"] != picked["cones"]  # (the records do show the switch)
+    assert picked["cones"] == {"z": 22, "l": 0, "q": [], "ep": 0, "s": [10]}
+    assert picked["kwarg_map"]["eps"] == "eps_abs" and set(picked["kwarg_map"].values()) <= sc._SCS_SETTINGS
+    assert sc._identify({"A": _csc(golden["g4_A"]), "b": golden["g4_b"]}, picked["cones"]) == _lib.VARIANT_FULL
 
 
 # ------------------------------------------------------------------------------------------------ GPU: the reference's own inputs

@@ -15,7 +15,7 @@ else
   for w in "--workload pnp_n4_50k" "--workload pnp_n10_125k" "--workload pnpl_5p5l_100k" "--workload pnp_scal --n 6" "--opt variant=1 --batch 50000"; do
   for i in $(seq ${2:-2}); do for v in $variants; do
     name=${v%%:*}
-    CVXPNPL_AMD_LIB=$GRAFT_REPO_ROOT/tools/diag/libcvxpnpl_$name.so timeout 300 python bench.py $w --no-cpu-baseline --pmc off --no-f64-ab 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', '$w', 'ms', round(d['roofline']['mean_launch_ms'],4), 'M/s', round(d['value']/1e6,2), '2-stream', round((d.get('overlapped') or {}).get('value',0)/1e6,2), d['solver']['status_hist'], 'iters', round(d['solver']['mean_iters'],3))"
+    CVXPNPL_AMD_LIB=$root/tools/diag/libcvxpnpl_$name.so timeout 300 python bench.py --full $w --no-cpu-baseline --pmc off --no-f64-ab 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read()); print('$name', '$w', 'ms', round(d['roofline']['mean_launch_ms'],4), 'M/s', round(d['value']/1e6,2), '2-stream', round((d.get('overlapped') or {}).get('value',0)/1e6,2), d['solver']['status_hist'], 'iters', round(d['solver']['mean_iters'],3))"
   done; done; done
   for v in $variants; do name=${v%%:*}; echo $name config5; CVXPNPL_AMD_LIB=$GRAFT_REPO_ROOT/tools/diag/libcvxpnpl_$name.so python tools/config5_sweep.py 2>/dev/null | head -2 | cut -c1-250; done
 fi

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 cd /tmp
 prof() { # name, bench args...
   name=$1; shift
-  CMD="python $root/bench.py --steps 20 --warmup 3 --no-cpu-baseline --no-overlap --pmc off $@"
+  CMD="python $root/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline --no-overlap --pmc off $@"
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/$name/trace -o trace -- $CMD > $out/$name.trace.log 2>&1
   timeout 600 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $out/$name/pmc_fetch -o fetch -- $CMD --pmc-child > $out/$name.fetch.log 2>&1
   timeout 600 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $out/$name/pmc_write -o write -- $CMD --pmc-child > $out/$name.write.log 2>&1
@@ -31,17 +31,17 @@ prof large_n --workload pnp_n10000_1k
 prof minimal_50k --workload pnp_n4_50k
 cd $root
 # bench lines of the same build (full default run incl. both CPU baselines and the in-run PMC passes)
-( time python bench.py > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_default.time
-python bench.py --batch 16000 --no-cpu-baseline > $out/bench_quad_16k.json 2>/dev/null
-python bench.py --workload pnp_n10_125k --no-cpu-baseline > $out/bench_125k.json 2>/dev/null
-python bench.py --workload pnpl_5p5l_100k --no-cpu-baseline > $out/bench_pnpl_100k.json 2>/dev/null
-python bench.py --workload pnp_n10000_1k --steps 20 > $out/bench_n10000_1k.json 2>/dev/null
-python bench.py --workload pnp_n10_125k --batch 1000000 --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_1m.json 2>/dev/null
-python bench.py --workload pnp_n4_50k --no-cpu-baseline > $out/bench_n4_50k.json 2>/dev/null
-python bench.py --workload ransac_n4_50k --no-cpu-baseline > $out/bench_ransac_n4_50k.json 2>/dev/null
-python bench.py --opt variant=1 --batch 50000 --no-cpu-baseline --pmc off > $out/bench_rc_50k.json 2>/dev/null
-python bench.py --force-dist --steps 20 --warmup 3 --no-cpu-baseline --pmc off > $out/bench_force_dist_1rank_rccl.json 2>/dev/null
-python bench.py --gpus 2 --steps 20 --warmup 3 > $out/bench_2ranks_one_device.json 2>/dev/null
+( time python bench.py --full > $out/bench_default.json 2> $out/bench_default.err ) 2> $out/bench_default.time
+python bench.py --full --batch 16000 --no-cpu-baseline > $out/bench_quad_16k.json 2>/dev/null
+python bench.py --full --workload pnp_n10_125k --no-cpu-baseline > $out/bench_125k.json 2>/dev/null
+python bench.py --full --workload pnpl_5p5l_100k --no-cpu-baseline > $out/bench_pnpl_100k.json 2>/dev/null
+python bench.py --full --workload pnp_n10000_1k --steps 20 > $out/bench_n10000_1k.json 2>/dev/null
+python bench.py --full --workload pnp_n10_125k --batch 1000000 --steps 10 --warmup 2 --no-cpu-baseline > $out/bench_1m.json 2>/dev/null
+python bench.py --full --workload pnp_n4_50k --no-cpu-baseline > $out/bench_n4_50k.json 2>/dev/null
+python bench.py --full --workload ransac_n4_50k --no-cpu-baseline > $out/bench_ransac_n4_50k.json 2>/dev/null
+python bench.py --full --opt variant=1 --batch 50000 --no-cpu-baseline --pmc off > $out/bench_rc_50k.json 2>/dev/null
+python bench.py --full --force-dist --steps 20 --warmup 3 --no-cpu-baseline --pmc off > $out/bench_force_dist_1rank_rccl.json 2>/dev/null
+python bench.py --full --gpus 2 --steps 20 --warmup 3 > $out/bench_2ranks_one_device.json 2>/dev/null
 python tools/config5_sweep.py > $out/config5_sweep.jsonl 2>/dev/null
 python tools/planar_timing.py > $out/planar_timing.jsonl 2>/dev/null
 python tools/iters_hist.py config5 2500 > $out/iters_config5.json 2>/dev/null

@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 mkdir -p gpurun_out/r05
 O=gpurun_out/r05/handoff_f64_sweep.txt; : > $O
-run() { timeout 600 python bench.py --precision f64 --no-f64-ab --no-cpu-baseline --pmc off --no-transfer --no-overlap $1 2>/dev/null | python -c "
+run() { timeout 600 python bench.py --full --precision f64 --no-f64-ab --no-cpu-baseline --pmc off --no-transfer --no-overlap $1 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read())
 print('$1', 'M/s', round(d['value']/1e6,2), 'ms', round(d['ms_per_step'],4), 'median', round(d.get('median_ms_per_step',0),4), d['solver']['status_hist'], 'iters', round(d['solver']['mean_iters'],3), d['solver']['max_iters_seen'])" >> $O; }
 for rep in 1 2; do

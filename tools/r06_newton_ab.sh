@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 n=${1:-2}; out=${2:-gpurun_out/r06/newton_ab.txt}
 mkdir -p $(dirname $out); : > $out
 one() { tag=$1; shift
-  timeout 300 python bench.py "$@" --no-cpu-baseline --pmc off --no-transfer --no-overlap 2>/dev/null | python -c "
+  timeout 300 python bench.py --full "$@" --no-cpu-baseline --pmc off --no-transfer --no-overlap 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); s=d['solver']
 print('$tag', '$*', 'ms', round(d['ms_per_step'],4), 'M/s', round(d['value']/1e6,2), 'mixed', round((d.get('value_mixed') or 0)/1e6,2), 'iters mean/max', round(s.get('mean_iters'),4), s.get('max_iters_seen'), s['status_hist'])" >> $out

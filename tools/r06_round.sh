@@ -15,6 +15,6 @@ bash tools/r06_ransac_kernels.sh > /dev/null 2>&1; tail -1 gpurun_out/r06/ransac
 python tools/r06_ransac_frames.py 60 > gpurun_out/r06/ransac_frames.txt 2>/dev/null; python tools/r06_ransac_frames.py 60 f64 >> gpurun_out/r06/ransac_frames.txt 2>/dev/null; cat gpurun_out/r06/ransac_frames.txt
 bash tools/r06_graph_gap.sh > /dev/null 2>&1; cat gpurun_out/r06/graph_gap/graph_gap.txt
 python tools/r06_refine_cost.py 2>/dev/null | grep problem > gpurun_out/r06/refine_cost.txt
-for s in 1 3 7; do python bench.py --seed $s --no-cpu-baseline --pmc off --no-transfer --no-overlap 2>/dev/null | python -c "
+for s in 1 3 7; do python bench.py --full --seed $s --no-cpu-baseline --pmc off --no-transfer --no-overlap 2>/dev/null | python -c "
 import sys,json; d=json.loads(sys.stdin.read()); print('seed $s', round(d['value']/1e6,2), round(d['value_mixed']/1e6,2), d['solver']['max_iters_seen'])"; done > gpurun_out/r06/bench_seeds.txt; cat gpurun_out/r06/bench_seeds.txt
 ls gpurun_out/r06 | wc -l

@@ -8,7 +8,7 @@ for n in /sys/devices/system/node/node[0-9]*; do echo "$(basename $n): cpus $(ca
 one() { # label, prefix...
   label=$1; shift
   for i in 1 2; do
-    "$@" python bench.py --no-cpu-baseline --pmc off --no-overlap --steps 100 2>/dev/null | python -c "
+    "$@" python bench.py --full --no-cpu-baseline --pmc off --no-overlap --steps 100 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read()); t=d['transfer_inclusive']
 print('$label', 'one_stream %.1f M' % (t['one_stream']['value']/1e6), 'two_streams %.1f M' % (t['two_streams']['value']/1e6), 'device on numa node', t['host_link'].get('numa_node'), t['host_link'].get('current_link_speed'), 'x' + str(t['host_link'].get('current_link_width')), '| resident %.1f M' % (d['value']/1e6))" >> $out
