@@ -141,6 +141,33 @@ def lib():
     return L
 
 
+# the backward pass (include/cvxpnpl_amd_grad.h): a library of its own beside the solver's
+GRAD_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_grad.so")
+GRAD_EXPORTS = ("cvxpnpl_pose_vjp_batch", "cvxpnpl_pose_vjp_host", "cvxpnpl_grad_last_error")
+VJP_OK, VJP_SKIPPED, VJP_SINGULAR, VJP_NONFINITE = 0, 1, 2, 3  # CVXPNPL_VJP_*
+
+_grad_lib = None
+
+
+def grad_lib():
+    """Load libcvxpnpl_amd_grad.so (loudly)."""
+    global _grad_lib
+    if _grad_lib is not None:
+        return _grad_lib
+    if not os.path.exists(GRAD_LIB_PATH):
+        raise LibraryMissing(f"{GRAD_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(GRAD_LIB_PATH)
+    L.cvxpnpl_pose_vjp_batch.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvxpnpl_pose_vjp_batch.restype = C.c_int
+    L.cvxpnpl_pose_vjp_host.argtypes = L.cvxpnpl_pose_vjp_batch.argtypes[:-1] + [C.c_int32]
+    L.cvxpnpl_pose_vjp_host.restype = C.c_int
+    L.cvxpnpl_grad_last_error.restype = C.c_char_p
+    _grad_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -35,22 +35,46 @@ def compile_cmd(out=OUT):
             "-mllvm", "-enable-ipra=0", "-o", out] + srcs
 
 
-def build(force=False, verbose=False):
-    deps = [d for d in DEPS if os.path.exists(d)]
-    fresh = os.path.exists(OUT) and os.path.getmtime(OUT) >= max(os.path.getmtime(d) for d in deps)
-    if not force and fresh and os.path.exists(RESOURCES) and os.path.getmtime(RESOURCES) >= os.path.getmtime(OUT):
-        return OUT
-    cmd = compile_cmd()
+# the backward pass of the solves (include/cvxpnpl_amd_grad.h): a library of its own, with its own resource remarks
+GRAD_SRC = os.path.join(HERE, "csrc", "grad_hip.hip")
+GRAD_HOST_SRC = os.path.join(HERE, "csrc", "host_vjp.cpp")
+GRAD_OUT = os.path.join(HERE, "libcvxpnpl_amd_grad.so")
+GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_grad.resources.txt")
+GRAD_DEPS = [GRAD_SRC, GRAD_HOST_SRC, os.path.join(HERE, "csrc", "vjp_core.h"), os.path.join(HERE, "csrc", "vjp_kernel.h"), os.path.join(HERE, "csrc", "solver_core.h"),
+             os.path.join(HERE, "csrc", "problem_io.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_grad.h")]
+
+
+def grad_compile_cmd(out=GRAD_OUT):
+    return [hipcc(), "-Rpass-analysis=kernel-resource-usage", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
+            "-o", out, GRAD_SRC, GRAD_HOST_SRC]
+
+
+def _build_one(out, resources, deps, cmd, force, verbose):
+    deps = [d for d in deps if os.path.exists(d)]
+    fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
+    if not force and fresh and os.path.exists(resources) and os.path.getmtime(resources) >= os.path.getmtime(out):
+        return out
     if verbose:
         print(" ".join(cmd))
     r = subprocess.run(cmd, stderr=subprocess.PIPE, text=True)
     if r.returncode != 0:
         sys.stderr.write(r.stderr[-8000:])
         raise subprocess.CalledProcessError(r.returncode, cmd)
-    with open(RESOURCES, "w") as f:
+    with open(resources, "w") as f:
         f.write(r.stderr)
     if verbose:
         sys.stderr.write(r.stderr)
+    return out
+
+
+def build_grad(force=False, verbose=False):
+    return _build_one(GRAD_OUT, GRAD_RESOURCES, GRAD_DEPS, grad_compile_cmd(), force, verbose)
+
+
+def build(force=False, verbose=False):
+    """Both libraries; returns the solver's (OUT)."""
+    _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
+    build_grad(force, verbose)
     return OUT
 
 
