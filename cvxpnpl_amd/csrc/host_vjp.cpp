@@ -47,7 +47,7 @@ extern "C" int cvxpnpl_pose_vjp_host(int64_t batch, int32_t n_p, const double *p
             for (int i = 0; i < n_p; ++i) cvxv::acc_point(acc, fr, pv.p2 + 2 * i, pv.p3 + 3 * i);
             for (int i = 0; i < n_l; ++i) cvxv::acc_line(acc, fr, pv.l2 + 4 * i, pv.l3 + 6 * i);
             double v[6];
-            const int st = cvxv::solve_v(acc, fr, gR ? gR + 9 * b : nullptr, gt ? gt + 3 * b : nullptr, v, info, vjp_info != nullptr);
+            const int st = cvxv::solve_v(acc, fr, n_p + n_l, gR ? gR + 9 * b : nullptr, gt ? gt + 3 * b : nullptr, v, info, vjp_info != nullptr);
             if (vjp_info) { vjp_info[2 * b] = info[0]; vjp_info[2 * b + 1] = info[1]; }
             vjp_status[b] = st;
             if (st != cvxv::VJP_OK) {

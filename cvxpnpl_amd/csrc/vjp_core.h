@@ -180,7 +180,10 @@ CVX_HD void eig_range6(const double *H, double &lo, double &hi)
 // From the reduced sums to v = H^-1 b (returned in v[6]; zeros unless VJP_OK).  gR [9] / gt [3] may be NULL (zero).
 // info [2] (filled when want_info): lambda_min(H) / lambda_max(H), and |g| / (2 sqrt(tr(H_gn) (f + 1e-20 scale))), which is <= 1 by
 // Cauchy-Schwarz and 0 at an exactly stationary pose.
-CVX_HD int solve_v(const Acc &a, const Frame &fr, const double *gR, const double *gt, double *v, double *info, bool want_info)
+// ncorr = points + lines.  Each gives two equations, so fewer than three determine no pose: VJP_SINGULAR whatever H looks like.  (At a
+// stationary pose the pivot test finds that by itself; away from one the second-order term lifts the null space of H_gn by about the
+// relative residual, far above PIVOT_TOL, and a meaningless v would pass for VJP_OK.)
+CVX_HD int solve_v(const Acc &a, const Frame &fr, int ncorr, const double *gR, const double *gt, double *v, double *info, bool want_info)
 {
     CVX_UNROLL for (int i = 0; i < 6; ++i) v[i] = 0.0;
     double H[36];
@@ -212,6 +215,7 @@ CVX_HD int solve_v(const Acc &a, const Frame &fr, const double *gR, const double
         info[1] = sqrt(gn) / (2.0 * sqrt(trH * (a.v[36] + 1e-20 * a.v[37])) + 1e-300);
     }
     if (!finite) return VJP_NONFINITE;
+    if (ncorr < 3) return VJP_SINGULAR;
     // Cholesky H = L L^T in place (lower triangle), pivot relative to its own diagonal entry
     double Lm[36];
     CVX_UNROLL for (int i = 0; i < 36; ++i) Lm[i] = H[i];

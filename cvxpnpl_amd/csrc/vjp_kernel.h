@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(VJP_TPB) vjp_group_kernel(VjpArgs a)
             acc.v[i] = x;
         }
         double info[2];
-        st = solve_v(acc, fr, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, v, info, INFO);
+        st = solve_v(acc, fr, a.n_p + a.n_l, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, v, info, INFO);
         if (INFO && lane == 0) { a.info[2 * b] = info[0]; a.info[2 * b + 1] = info[1]; }
     } else if (INFO && lane == 0) {
         a.info[2 * b] = NAN; a.info[2 * b + 1] = NAN;
@@ -145,7 +145,7 @@ __global__ void __launch_bounds__(64) vjp_solve_kernel(VjpArgs a, int nblk, cons
             const double *p = partial + ((int64_t)b * nblk + k) * ACC_N;
             CVX_UNROLL for (int i = 0; i < ACC_N; ++i) acc.v[i] += p[i];
         }
-        st = solve_v(acc, fr, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, v, info, a.info != nullptr);
+        st = solve_v(acc, fr, a.n_p + a.n_l, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, v, info, a.info != nullptr);
     }
     if (a.info) { a.info[2 * b] = info[0]; a.info[2 * b + 1] = info[1]; }
     a.vstatus[b] = st;

@@ -37,7 +37,8 @@ extern "C" {
 enum {
     CVXPNPL_VJP_OK = 0,
     CVXPNPL_VJP_SKIPPED = 1,  /* status not in admit_mask */
-    CVXPNPL_VJP_SINGULAR = 2, /* H not positive definite (a Cholesky pivot below 1e-11 of its diagonal entry): degenerate configuration */
+    CVXPNPL_VJP_SINGULAR = 2, /* H not positive definite (a Cholesky pivot below 1e-11 of its diagonal entry): degenerate configuration;
+                                 or fewer than three correspondences (n_p + n_l < 3: under six equations determine no pose) */
     CVXPNPL_VJP_NONFINITE = 3 /* NaN / inf in the pose, the inputs or the solve */
 };
 int cvxpnpl_pose_vjp_batch(int64_t batch, int32_t n_p, const double *d_pts_2d, const double *d_pts_3d, int32_t n_l, const double *d_line_2d,

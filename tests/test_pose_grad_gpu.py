@@ -2,7 +2,10 @@
 
 The device kernels and the host loop (cvxpnpl_pose_vjp_host, checked against finite differences in test_pose_grad_host.py) are one
 source (vjp_core.h); only the order of the sums differs, so they agree to 1e-10 relative at the GPU's own poses -- in both regimes
-(16 lanes per problem; the multi-workgroup reduction from 768 records on).
+(16 lanes per problem; the multi-workgroup reduction from 768 records on).  Every status here comes from a real solve, where nearly
+all problems certify: the skipped, singular and non-finite problems of either regime, the regime boundary, the workgroup tails, absent
+arguments, side streams and the comparison with an independent reference are in test_pose_grad_gpu_edges.py (the reference itself
+in grad_reference.py, the host twin against it in test_pose_grad_reference.py).
 """
 import numpy as np
 import pytest

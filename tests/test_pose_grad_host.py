@@ -9,63 +9,12 @@ solve_v), every case below misses this tolerance by orders of magnitude -- relat
 """
 import numpy as np
 import pytest
+from grad_reference import polish  # the test's own local solver (shared with test_pose_grad_reference.py)
 
 from cvxpnpl_amd import synth
 from cvxpnpl_amd.grad import ADMIT_CERTIFIED, ADMIT_RANK1, pose_vjp_host
 
 K_GENERAL = np.array([[510.0, 2.5, 301.0], [0.0, 540.0, 262.0], [0.0, 0.0, 1.0]])
-
-
-def _hat(w):
-    return np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
-
-
-def _expm(w):
-    th = np.linalg.norm(w)
-    W = _hat(w)
-    if th < 1e-8:
-        return np.eye(3) + W + 0.5 * W @ W
-    return np.eye(3) + np.sin(th) / th * W + (1.0 - np.cos(th)) / th ** 2 * W @ W
-
-
-def _rows(R, t, p2, p3, l2, l3, Ki):
-    """Residual rows A_i (R X_i + t) as (A [m,3], X [m,3])."""
-    A, X = [], []
-    for uv, P in zip(p2, p3):
-        p = Ki @ np.array([uv[0], uv[1], 1.0])
-        A.append(_hat(p))
-        X.append(np.repeat(P[None], 3, 0))
-    for seg, ends in zip(l2, l3):
-        a = Ki @ np.array([seg[0, 0], seg[0, 1], 1.0])
-        b = Ki @ np.array([seg[1, 0], seg[1, 1], 1.0])
-        n = np.cross(a, b)
-        n /= np.linalg.norm(n)
-        for E in ends:
-            A.append(n[None])
-            X.append(E[None])
-    return np.concatenate(A), np.concatenate(X)
-
-
-def polish(R, t, p2, p3, l2, l3, K, iters=60):
-    """Gauss-Newton on the algebraic cost about the centroid c of the 3D records (X -> exp(w) R (X - c) + tc + tau) until the step is
-    at rounding level.  Returns R, t and the final |g| relative to its Cauchy-Schwarz bound."""
-    Ki = np.linalg.inv(K)
-    A, X = _rows(R, t, p2, p3, l2, l3, Ki)
-    c = X.mean(0)
-    tc = R @ c + t
-    for _ in range(iters):
-        y = (X - c) @ R.T
-        z = y + tc
-        r = np.einsum("ij,ij->i", A, z)
-        J = np.concatenate([np.cross(y, A), A], 1)  # d/dw of a.(exp(w) y) = a.(w x y) = w.(y x a)
-        g = 2 * J.T @ r
-        step = -np.linalg.solve(J.T @ J, J.T @ r)
-        R = _expm(step[:3]) @ R
-        tc = tc + step[3:]
-        if np.abs(step).max() < 1e-17 * (1 + np.abs(tc).max()):
-            break
-    t = tc - R @ c
-    return R, t, np.linalg.norm(g) / (2 * np.sqrt((J ** 2).sum() * (r @ r)) + 1e-300)
 
 
 def _case(kind, n, seed, K=synth.K_KINECT, far=None):
