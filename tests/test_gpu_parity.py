@@ -5,8 +5,15 @@ size-independent properties.  Run with -m gpu on an MI355X.
 Tolerances (float64 path): rotation geodesic <= 1e-6 rad and relative translation <= 1e-6
 against the oracle / ground truth (the north-star tolerance); in practice ~1e-9 (the
 oracle's own convergence) and ~1e-14 against noise-free ground truth."""
+import os
+import sys
+
 import numpy as np
 import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from certificate_audit import reference_A_B as _reference_A_B  # noqa: E402  (the helper moved there, unchanged)
 
 pytestmark = pytest.mark.gpu
 
@@ -51,21 +58,6 @@ def _oracle_case(orc, d, n_p, n_l, key):
         _ORACLE_CACHE[key] = orc.pnpl_batch(d["pts_2d"] if n_p else None, d["line_2d"] if n_l else None, d["pts_3d"] if n_p else None,
                                             d["line_3d"] if n_l else None, d["K"], eps=1e-11, max_iters=200000)
     return _ORACLE_CACHE[key]
-
-
-def _reference_A_B(orc, d, i, n_p, n_l):
-    """A (m x 9), B (3 x 9) of problem i the way cvxpnpl.pnp / pnl / pnpl build them (cvxpnpl.py:545-549, :577-580, :619-624)"""
-    Cs, Ns = [], []
-    if n_p:
-        (c1, c2, c3), (n1, n2, n3) = orc.point_constraints(d["pts_2d"][i], d["pts_3d"][i], d["K"] if d["K"].ndim == 2 else d["K"][i])
-        Cs += [c1, c2, c3]
-        Ns += [n1, n2, n3]
-    if n_l:
-        cl, nl = orc.line_constraints(d["line_2d"][i], d["line_3d"][i], d["K"] if d["K"].ndim == 2 else d["K"][i])
-        Cs.append(cl)
-        Ns.append(nl)
-    B, A = orc.eliminate(np.vstack(Cs), np.vstack(Ns))
-    return A, B
 
 
 def _check_uncertified_exits(orc, d, r, n_p, n_l, idx):
