@@ -168,6 +168,35 @@ def grad_lib():
     return L
 
 
+# RANSAC over many scenes (include/cvxpnpl_amd_ransac.h): the third library
+RANSAC_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac.so")
+RANSAC_EXPORTS = ("cvxpnpl_ransac_sample_scenes", "cvxpnpl_ransac_score_scenes", "cvxpnpl_ransac_select_scenes", "cvxpnpl_ransac_assemble_consensus",
+                  "cvxpnpl_ransac_refit_update_scenes", "cvxpnpl_ransac_last_error")
+
+_ransac_lib = None
+
+
+def ransac_lib():
+    """Load libcvxpnpl_amd_ransac.so (loudly)."""
+    global _ransac_lib
+    if _ransac_lib is not None:
+        return _ransac_lib
+    if not os.path.exists(RANSAC_LIB_PATH):
+        raise LibraryMissing(f"{RANSAC_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(RANSAC_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.cvxpnpl_ransac_sample_scenes.argtypes = [i64, i32, p, i64, p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_score_scenes.argtypes = [i64, i32, p, i64, p, p, p, C.c_uint32, p, i32, p, p, C.c_double, p, p]
+    L.cvxpnpl_ransac_select_scenes.argtypes = [i64, i32, p, i64, p, p, p, p, p, i32, p, p, C.c_double, p, p, p, p, p]
+    L.cvxpnpl_ransac_assemble_consensus.argtypes = [i64, p, i64, p, p, p, p, i32, p, p, p, p]
+    L.cvxpnpl_ransac_refit_update_scenes.argtypes = [i64, p, i64, p, p, p, p, p, i32, p, p, C.c_double, p, p, p, p, p]
+    for name in RANSAC_EXPORTS[:-1]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_ransac_last_error.restype = C.c_char_p
+    _ransac_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

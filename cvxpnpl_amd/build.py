@@ -49,6 +49,19 @@ def grad_compile_cmd(out=GRAD_OUT):
             "-o", out, GRAD_SRC, GRAD_HOST_SRC]
 
 
+# RANSAC over many scenes (include/cvxpnpl_amd_ransac.h): the third library, with its own resource remarks
+RANSAC_SRC = os.path.join(HERE, "csrc", "ransac_hip.hip")
+RANSAC_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac.so")
+RANSAC_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac.resources.txt")
+RANSAC_DEPS = [RANSAC_SRC, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+               os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac.h")]
+
+
+def ransac_compile_cmd(out=RANSAC_OUT):
+    return [hipcc(), "-Rpass-analysis=kernel-resource-usage", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
+            "-o", out, RANSAC_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -71,10 +84,15 @@ def build_grad(force=False, verbose=False):
     return _build_one(GRAD_OUT, GRAD_RESOURCES, GRAD_DEPS, grad_compile_cmd(), force, verbose)
 
 
+def build_ransac(force=False, verbose=False):
+    return _build_one(RANSAC_OUT, RANSAC_RESOURCES, RANSAC_DEPS, ransac_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """Both libraries; returns the solver's (OUT)."""
+    """All three libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
+    build_ransac(force, verbose)
     return OUT
 
 

@@ -1,0 +1,392 @@
+// ransac_kernel.h -- RANSAC over MANY scenes of different sizes in one launch sequence (include/cvxpnpl_amd_ransac.h, DESIGN.md
+// section 13).  score_kernel.h holds the same five steps for ONE scene; here scene f is the slice off[f] .. off[f+1] of the packed
+// correspondences [n_total][2] / [n_total][3], every scene draws the same number H of hypotheses, and hypothesis (f, h) is problem
+// f * H + h of the minimal solve.  Only the scenes are ragged, and a scene is only ever streamed.
+//
+// Every kernel clamps a scene's slice to [0, n_total): offsets live on the device and cannot be checked by the host entry points, and
+// a wrong one must not become a store outside the packed mask.  All loops are bounded by H, M_f or a constant.
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "problem_io.h"
+#include "solver_core.h"
+
+namespace cvxn {
+
+constexpr int SCENE_BLOCK = 256;  // lanes of the sampling / scoring / selection / refit workgroups
+constexpr int SCENE_TILE = 512;   // correspondences per LDS tile of the scoring kernel (20 KB)
+constexpr int SCENE_WAVES = SCENE_BLOCK / 64;
+
+struct Slice { int64_t beg; int32_t n; };
+__device__ inline Slice scene_slice(const int64_t *off, int64_t f, int64_t n_total)
+{
+    int64_t e = off[f + 1], b = off[f];
+    e = e < 0 ? 0 : (e > n_total ? n_total : e);
+    b = b < 0 ? 0 : (b > e ? e : b);
+    const int64_t n = e - b;
+    return Slice{b, (int32_t)(n > 0x7fffffffLL ? 0x7fffffffLL : n)};
+}
+
+// ---- the inlier predicate: ONE statement of it, used by the scoring kernel (counts) and by the two workgroup kernels (masks), so
+// that a mask and a count cannot disagree.  The arithmetic is that of cvxs::score_kernel / cvxs::block_score_pose, expression by
+// expression:  X = R P + t,  (u, v, w) = K X,  depth = X_z > 0,  |(u / w, v / w) - x|^2 < thresh^2;  a NaN pose compares false.
+struct Camera {
+    double M[12];      // K R | K t : pixel-space projection
+    double r2[3], t2;  // depth row
+};
+__device__ inline void camera_load(const double *Rp, const double *tp, const double *Kp, Camera &c)
+{
+    double R[9], t[3], K[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) { R[i] = Rp[i]; K[i] = Kp[i]; }
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = tp[i];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c.M[i * 4 + j] = K[i * 3] * R[j] + K[i * 3 + 1] * R[3 + j] + K[i * 3 + 2] * R[6 + j];
+        c.M[i * 4 + 3] = K[i * 3] * t[0] + K[i * 3 + 1] * t[1] + K[i * 3 + 2] * t[2];
+    }
+    c.r2[0] = R[6]; c.r2[1] = R[7]; c.r2[2] = R[8]; c.t2 = t[2];
+}
+__device__ inline bool is_inlier(const Camera &c, double X, double Y, double Z, double x, double y, double th2)
+{
+    const double u = c.M[0] * X + c.M[1] * Y + c.M[2] * Z + c.M[3];
+    const double v = c.M[4] * X + c.M[5] * Y + c.M[6] * Z + c.M[7];
+    const double w = c.M[8] * X + c.M[9] * Y + c.M[10] * Z + c.M[11];
+    const double depth = c.r2[0] * X + c.r2[1] * Y + c.r2[2] * Z + c.t2;
+    const double du = u / w - x, dv = v / w - y;
+    return depth > 0.0 && (du * du + dv * dv < th2);
+}
+
+// ---- sampling: one lane per (scene, hypothesis), grid (ceil(H / 256), scenes).  The draw of cvxs::sample_sets_kernel for k = 4 over the
+// scene's own M_f, with the scene's own seed as the Philox key and the hypothesis index WITHIN the scene as the counter: scene f draws
+// what cvxpnpl_sample_minimal_sets(scene f, H, 4, seed_f) draws.
+struct SampleScenesArgs {
+    int64_t scene0, n_scenes, n_total;
+    int32_t n_hyp;
+    const int64_t *off;
+    const uint64_t *seed;    // [n_scenes]
+    const double *s2, *s3;   // packed scenes
+    const double *K;         // [n_scenes][9] or null
+    int32_t *idx;            // [n_scenes * n_hyp][4] (optional)
+    double *p2, *p3;         // [n_scenes * n_hyp][4][2], [..][4][3]
+    double *Kh;              // [n_scenes * n_hyp][9] (with K)
+};
+__device__ inline void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t *out)
+{
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n1 = (uint32_t)p1, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1, n3 = (uint32_t)p0;
+        c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+__global__ void __launch_bounds__(SCENE_BLOCK) sample_scenes_kernel(SampleScenesArgs a)
+{
+    const int64_t f = a.scene0 + blockIdx.y;
+    const int32_t h = (int32_t)(blockIdx.x * SCENE_BLOCK + threadIdx.x);
+    if (f >= a.n_scenes || h >= a.n_hyp) return;
+    const Slice sl = scene_slice(a.off, f, a.n_total);
+    const int64_t g = f * a.n_hyp + h;
+    if (a.Kh) {
+#pragma unroll
+        for (int i = 0; i < 9; ++i) a.Kh[g * 9 + i] = a.K[f * 9 + i];
+    }
+    if (sl.n < 4) { // (refused by the Python entry point; here: no draw is possible, the solve reports a non-finite pose)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            if (a.idx) a.idx[g * 4 + j] = -1;
+            a.p2[(g * 4 + j) * 2] = NAN; a.p2[(g * 4 + j) * 2 + 1] = NAN;
+            a.p3[(g * 4 + j) * 3] = NAN; a.p3[(g * 4 + j) * 3 + 1] = NAN; a.p3[(g * 4 + j) * 3 + 2] = NAN;
+        }
+        return;
+    }
+    const uint64_t seed = a.seed[f];
+    uint32_t w[4];
+    philox4x32((uint32_t)h, 0u, 0xFFFFFFFEu, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
+    int pos[4], val[4], pick[4]; // positions already swapped and what sits there now (static indices: registers)
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const uint32_t span = (uint32_t)(sl.n - j);
+        const int r = j + (int)(((uint64_t)w[j] * span) >> 32); // uniform on j .. M_f - 1
+        int vr = r, vj = j;
+#pragma unroll
+        for (int m = 0; m < j; ++m) {
+            vr = pos[m] == r ? val[m] : vr;
+            vj = pos[m] == j ? val[m] : vj;
+        }
+        pick[j] = vr;
+        pos[j] = r; val[j] = vj;
+#pragma unroll
+        for (int m = 0; m < j; ++m) // a later entry for the same position overrides an earlier one
+            if (pos[m] == r) pos[m] = -1;
+    }
+    const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int c = pick[j]; // 0 .. M_f - 1 by construction
+        if (a.idx) a.idx[g * 4 + j] = c;
+        a.p2[(g * 4 + j) * 2] = s2[c * 2]; a.p2[(g * 4 + j) * 2 + 1] = s2[c * 2 + 1];
+        a.p3[(g * 4 + j) * 3] = s3[c * 3]; a.p3[(g * 4 + j) * 3 + 1] = s3[c * 3 + 1]; a.p3[(g * 4 + j) * 3 + 2] = s3[c * 3 + 2];
+    }
+}
+
+// ---- scoring: grid (ceil(H / 256), scenes), one lane per hypothesis of the workgroup's scene; the scene is staged through LDS a tile at
+// a time and broadcast to the lanes, as cvxs::score_kernel does.  count [n_scenes * n_hyp].
+struct ScoreScenesArgs {
+    int64_t scene0, n_scenes, n_total;
+    int32_t n_hyp;
+    const int64_t *off;
+    const double *R, *t;     // [n_scenes * n_hyp][9], [..][3]
+    const int32_t *status;   // optional
+    uint32_t usable_mask;    // bit s set: status s is scored
+    const double *K;         // [9] or [n_scenes][9]
+    int32_t K_per_scene;
+    const double *s2, *s3;
+    double thresh;
+    int32_t *count;
+};
+__global__ void __launch_bounds__(SCENE_BLOCK) score_scenes_kernel(ScoreScenesArgs a)
+{
+    __shared__ double scene[SCENE_TILE * 5];
+    const int64_t f = a.scene0 + blockIdx.y;
+    if (f >= a.n_scenes) return; // (block-uniform)
+    const int32_t h = (int32_t)(blockIdx.x * SCENE_BLOCK + threadIdx.x);
+    const bool live = h < a.n_hyp;
+    const int64_t g = f * a.n_hyp + (live ? h : 0);
+    const Slice sl = scene_slice(a.off, f, a.n_total);
+    Camera cam;
+    camera_load(a.R + g * 9, a.t + g * 3, a.K + (a.K_per_scene ? f * 9 : 0), cam);
+    bool usable = live;
+    if (live && a.status) {
+        const int32_t s = a.status[g];
+        usable = s >= 0 && s < 32 && ((a.usable_mask >> s) & 1u);
+    }
+    const double th2 = a.thresh * a.thresh;
+    const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
+    int cnt = 0;
+    for (int base = 0; base < sl.n; base += SCENE_TILE) {
+        const int n = sl.n - base < SCENE_TILE ? sl.n - base : SCENE_TILE;
+        __syncthreads();
+        for (int i = threadIdx.x; i < n; i += SCENE_BLOCK) {
+            const int64_t m = base + i;
+            scene[i * 5 + 0] = s3[m * 3 + 0];
+            scene[i * 5 + 1] = s3[m * 3 + 1];
+            scene[i * 5 + 2] = s3[m * 3 + 2];
+            scene[i * 5 + 3] = s2[m * 2 + 0];
+            scene[i * 5 + 4] = s2[m * 2 + 1];
+        }
+        __syncthreads();
+        for (int i = 0; i < n; ++i)
+            cnt += usable && is_inlier(cam, scene[i * 5], scene[i * 5 + 1], scene[i * 5 + 2], scene[i * 5 + 3], scene[i * 5 + 4], th2) ? 1 : 0;
+    }
+    if (live) a.count[g] = cnt;
+}
+
+// inliers of ONE pose over one scene, by the lanes of one workgroup: writes mask (optional) and returns the count to every lane
+__device__ inline int block_inliers(const Camera &cam, int n, const double *s2, const double *s3, double th2, uint8_t *mask, int *red /* LDS, SCENE_WAVES ints */)
+{
+    int cnt = 0;
+    for (int m = threadIdx.x; m < n; m += SCENE_BLOCK) {
+        const bool in = is_inlier(cam, s3[3 * m], s3[3 * m + 1], s3[3 * m + 2], s2[2 * m], s2[2 * m + 1], th2);
+        cnt += in ? 1 : 0;
+        if (mask) mask[m] = in ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    int tot = 0;
+#pragma unroll
+    for (int wv = 0; wv < SCENE_WAVES; ++wv) tot += red[wv];
+    return tot;
+}
+
+// ---- selection: ONE workgroup per scene.  Arg-max of the scene's H counts with the LOWEST index winning a tie, the number of certified
+// hypotheses on the way, then the winner's pose and -- scored again by the workgroup's lanes -- its mask in the scene's slice of the
+// packed mask.  head[f] = { status of the pose, inliers, index of the winner within the scene, certified hypotheses }.
+struct SelectScenesArgs {
+    int64_t n_scenes, n_total;
+    int32_t n_hyp;
+    const int64_t *off;
+    const int32_t *count;    // [n_scenes * n_hyp]
+    const double *R, *t;
+    const int32_t *status;
+    const double *K;
+    int32_t K_per_scene;
+    const double *s2, *s3;
+    double thresh;
+    double *out_R, *out_t;   // [n_scenes][9], [n_scenes][3]
+    int32_t *head;           // [n_scenes][4]
+    uint8_t *mask;           // [n_total]
+};
+__global__ void __launch_bounds__(SCENE_BLOCK) select_scenes_kernel(SelectScenesArgs a)
+{
+    __shared__ int red[SCENE_WAVES];
+    __shared__ long long best_w[SCENE_WAVES];
+    __shared__ int cert_w[SCENE_WAVES];
+    const int64_t f = blockIdx.x;
+    if (f >= a.n_scenes) return;
+    const int64_t g0 = f * a.n_hyp;
+    // (count, index) packed so that a plain max picks the highest count and, among equals, the LOWEST index
+    long long best = -1;
+    int cert = 0;
+    for (int h = threadIdx.x; h < a.n_hyp; h += SCENE_BLOCK) {
+        const long long key = ((long long)a.count[g0 + h] << 32) | (long long)(0x7fffffff - h);
+        best = key > best ? key : best;
+        cert += a.status[g0 + h] == 0 ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        const long long ob = __shfl_down(best, o);
+        best = ob > best ? ob : best;
+        cert += __shfl_down(cert, o);
+    }
+    if ((threadIdx.x & 63) == 0) { best_w[threadIdx.x >> 6] = best; cert_w[threadIdx.x >> 6] = cert; }
+    __syncthreads();
+    best = best_w[0]; cert = cert_w[0];
+#pragma unroll
+    for (int wv = 1; wv < SCENE_WAVES; ++wv) { best = best_w[wv] > best ? best_w[wv] : best; cert += cert_w[wv]; }
+    int hb = (int)(0x7fffffffLL - (best & 0xffffffffLL));
+    hb = hb < 0 || hb >= a.n_hyp ? 0 : hb; // (a negative count cannot win; a corrupt one must not index outside the scene's hypotheses)
+    const int64_t gb = g0 + hb;
+    const Slice sl = scene_slice(a.off, f, a.n_total);
+    Camera cam;
+    camera_load(a.R + gb * 9, a.t + gb * 3, a.K + (a.K_per_scene ? f * 9 : 0), cam);
+    const int n_inl = block_inliers(cam, sl.n, a.s2 + sl.beg * 2, a.s3 + sl.beg * 3, a.thresh * a.thresh, a.mask + sl.beg, red);
+    if (threadIdx.x < 9) a.out_R[f * 9 + threadIdx.x] = a.R[gb * 9 + threadIdx.x];
+    if (threadIdx.x < 3) a.out_t[f * 3 + threadIdx.x] = a.t[gb * 3 + threadIdx.x];
+    if (threadIdx.x == 0) { a.head[f * 4] = a.status[gb]; a.head[f * 4 + 1] = n_inl; a.head[f * 4 + 2] = hb; a.head[f * 4 + 3] = cert; }
+}
+
+// ---- consensus assembly: ONE wavefront per scene.  (cvxpnpl_assemble_subsets gives a subset to one lane, which streams the scene
+// serially: the wrong shape for a few hundred scenes of 10^3 correspondences.)  The lanes stride over the scene's correspondences, each
+// with Gram sums of its own; the sums meet in a fixed-order XOR butterfly, after which every lane holds the same total -- the result
+// does not depend on anything but the inputs.  The centre of the sums is the median of the subset's own first three selected records
+// (cvx::shift_centre; any centre is exact).  Fewer than three selected: NaN, as cvx::assemble reports a singular N^T N.
+struct ConsensusArgs {
+    int64_t n_scenes, n_total;
+    const int64_t *off;
+    const double *s2, *s3;
+    const uint8_t *mask;     // [n_total]
+    const double *K;
+    int32_t K_per_scene;
+    double *B27, *Q45;       // [n_scenes][27], [n_scenes][45]
+    int32_t *count;          // [n_scenes]
+};
+__device__ inline double wave_xor_add(double v, int o) { return v + __shfl_xor(v, o); }
+__global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
+{
+    const int64_t f = blockIdx.x;
+    if (f >= a.n_scenes) return;
+    const int lane = threadIdx.x;
+    const Slice sl = scene_slice(a.off, f, a.n_total);
+    const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
+    const uint8_t *mk = a.mask + sl.beg;
+    double Kc[9], Ki[9], det;
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Kc[i] = a.K[(a.K_per_scene ? f * 9 : 0) + i];
+    cvx::inv3(Kc, Ki, det);
+    // the first three selected correspondences, in scene order: ballots over chunks of 64 (wave-uniform)
+    int first[3] = {0, 0, 0}, nf = 0;
+    for (int base = 0; base < sl.n && nf < 3; base += 64) {
+        const int m = base + lane;
+        unsigned long long b = __ballot(m < sl.n && mk[m] != 0);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            if (b != 0 && nf < 3) {
+                const int pos = base + __ffsll((long long)b) - 1;
+                first[0] = nf == 0 ? pos : first[0]; first[1] = nf == 1 ? pos : first[1]; first[2] = nf == 2 ? pos : first[2];
+                ++nf;
+                b &= b - 1;
+            }
+        }
+    }
+    double c[3] = {0.0, 0.0, 0.0};
+    if (nf > 0) {
+        double first3[9];
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { // (entries beyond nf repeat the first record and are not read by shift_centre)
+            const int m = k < nf ? first[k] : first[0];
+            first3[3 * k] = s3[3 * m]; first3[3 * k + 1] = s3[3 * m + 1]; first3[3 * k + 2] = s3[3 * m + 2];
+        }
+        cvx::shift_centre(nf, first3, 0, nullptr, c);
+    }
+    cvx::Gram g;
+    cvx::gram_zero(g);
+    int n = 0;
+    for (int m = lane; m < sl.n; m += 64) {
+        if (!mk[m]) continue;
+        cvx::gram_add_point(g, Ki, s2[2 * m], s2[2 * m + 1], s3[3 * m] - c[0], s3[3 * m + 1] - c[1], s3[3 * m + 2] - c[2]);
+        ++n;
+    }
+#pragma unroll 1
+    for (int o = 1; o < 64; o <<= 1) { // (rolled: six passes over the same 60 sums)
+#pragma unroll
+        for (int i = 0; i < 6; ++i) g.M0[i] = wave_xor_add(g.M0[i], o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) g.M1[k][i] = wave_xor_add(g.M1[k][i], o);
+#pragma unroll
+        for (int k = 0; k < 6; ++k)
+#pragma unroll
+            for (int i = 0; i < 6; ++i) g.M2[k][i] = wave_xor_add(g.M2[k][i], o);
+        n += __shfl_xor(n, o);
+    }
+    double B[27], Q9[45];
+    const bool ok = n >= 3 && cvx::gram_finish(g, B, Q9) && (det == det) && det != 0.0;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) B[i * 9 + 3 * j + i] += c[j];
+    if (lane == 0) { // (every lane holds the same values; static indices keep B and Q9 in registers)
+#pragma unroll
+        for (int i = 0; i < 27; ++i) a.B27[f * 27 + i] = ok ? B[i] : NAN;
+#pragma unroll
+        for (int i = 0; i < 45; ++i) a.Q45[f * 45 + i] = ok ? Q9[i] : NAN;
+        a.count[f] = n;
+    }
+}
+
+// ---- refit update: ONE workgroup per scene, the rule of cvxs::refit_update_kernel.  The refitted pose of the scene's consensus set is
+// scored against the scene and TAKEN -- pose, status, mask and count together -- when it is usable (status 0 or 2, fitted to at least
+// four correspondences) and keeps at least the consensus it was fitted to; otherwise everything of the scene stays.
+struct RefitScenesArgs {
+    int64_t n_scenes, n_total;
+    const int64_t *off;
+    const double *fit_R, *fit_t;   // [n_scenes][9], [n_scenes][3]
+    const int32_t *fit_status;     // [n_scenes]
+    const int32_t *fit_cnt;        // [n_scenes] size of the set each was fitted to
+    const double *K;
+    int32_t K_per_scene;
+    const double *s2, *s3;
+    double thresh;
+    double *io_R, *io_t;
+    int32_t *head;                 // [n_scenes][4]
+    uint8_t *mask;                 // [n_total]
+};
+__global__ void __launch_bounds__(SCENE_BLOCK) refit_update_scenes_kernel(RefitScenesArgs a)
+{
+    __shared__ int red[SCENE_WAVES];
+    const int64_t f = blockIdx.x;
+    if (f >= a.n_scenes) return;
+    const Slice sl = scene_slice(a.off, f, a.n_total);
+    const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
+    Camera cam;
+    camera_load(a.fit_R + f * 9, a.fit_t + f * 3, a.K + (a.K_per_scene ? f * 9 : 0), cam);
+    const double th2 = a.thresh * a.thresh;
+    const int st = a.fit_status[f];
+    const int n_new = block_inliers(cam, sl.n, s2, s3, th2, nullptr, red);
+    const bool take = (st == 0 || st == 2) && a.fit_cnt[f] >= 4 && n_new >= a.head[f * 4 + 1]; // (workgroup-uniform)
+    __syncthreads();
+    if (!take) return;
+    (void)block_inliers(cam, sl.n, s2, s3, th2, a.mask + sl.beg, red); // pose and mask change together
+    if (threadIdx.x < 9) a.io_R[f * 9 + threadIdx.x] = a.fit_R[f * 9 + threadIdx.x];
+    if (threadIdx.x < 3) a.io_t[f * 3 + threadIdx.x] = a.fit_t[f * 3 + threadIdx.x];
+    if (threadIdx.x == 0) { a.head[f * 4] = st; a.head[f * 4 + 1] = n_new; }
+}
+
+} // namespace cvxn

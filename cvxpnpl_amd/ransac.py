@@ -6,10 +6,14 @@ reprojection inliers over the whole scene, refit the best consensus set (assembl
 solved at the cost seam: no host round trip inside a frame).  Sampling, the solves and the scoring are the HIP path (cvxpnpl_sample_minimal_sets, cvxpnpl_solve_batch,
 cvxpnpl_score_hypotheses, cvxpnpl_select_best, cvxpnpl_assemble_subsets, cvxpnpl_solve_cost_batch, cvxpnpl_refit_update): no torch kernel in a frame.
 """
+import ctypes as _C
 from typing import Optional
 
+import numpy as _np
 import torch
 
+from . import _lib
+from .api import _ptr, _require_gpu
 from .api import assemble_subsets, pnp_batch, refit_update, sample_minimal_sets, score_hypotheses, select_best, solve_cost_batch
 
 
@@ -61,3 +65,277 @@ def ransac_pnp(pts_2d, pts_3d, K, n_hyp: int = 4096, thresh: float = 2.0, max_it
     h = head.cpu()   # the frame's one synchronisation
     return {"R": R[0], "t": t[0], "inliers": mask[0].bool(), "n_inliers": int(h[1]), "status": int(h[0]), "n_certified": int(h[3]), "n_hyp": n_hyp,
             "best_index": int(h[2])}
+
+
+# ---- many scenes of different sizes in one launch sequence (include/cvxpnpl_amd_ransac.h) -------------------------
+# ransac_pnp above handles one scene per call: ~16 launches and one read-back per frame, which at a realistic budget of a few hundred
+# hypotheses is almost pure launch latency.  Here F scenes share every launch: F * n_hyp minimal solves in ONE cvxpnpl_solve_batch, F
+# refits in ONE cvxpnpl_solve_cost_batch, and the steps around them in the kernels of libcvxpnpl_amd_ransac.so, which address scene f
+# through a device array of offsets into the packed correspondences.
+
+
+class Scenes:
+    """F scenes packed on one device: x [total,2], X [total,3] float64, offsets [F+1] int64 (device), sizes (host tuple), K [3,3] or
+    [F,3,3], per_scene_K; seeds: the scenes' sampling seeds as int64 [F] on the device, or None.  Built by pack_scenes."""
+
+    def __init__(self, x, X, offsets, sizes, K, seeds=None):
+        self.x, self.X, self.offsets, self.sizes, self.K, self.seeds = x, X, offsets, tuple(sizes), K, seeds
+        self.F, self.total, self.per_scene_K, self.device = len(self.sizes), int(sum(self.sizes)), int(K.dim() == 3), x.device
+
+
+def _shape(a):
+    return tuple(a.shape) if hasattr(a, "shape") else _np.shape(a)
+
+
+def _check_scenes(pts_2d, pts_3d, K, sizes):
+    """Host-side validation of a scene set (nothing here needs a GPU): returns the sizes.  ValueError for an empty set, a scene of fewer
+    than four correspondences, 2D / 3D lengths that differ, sizes that do not add up, or a K that is neither [3,3] nor [F,3,3]."""
+    if sizes is None:
+        if not isinstance(pts_2d, (list, tuple)) or not isinstance(pts_3d, (list, tuple)):
+            raise ValueError("scenes are a list of [M_f,2] and a list of [M_f,3] arrays, or packed [sum M,2] / [sum M,3] arrays with `sizes`")
+        if len(pts_2d) != len(pts_3d):
+            raise ValueError(f"{len(pts_2d)} scenes of 2D points for {len(pts_3d)} scenes of 3D points")
+        sizes = []
+        for f, (a, b) in enumerate(zip(pts_2d, pts_3d)):
+            sa, sb = _shape(a), _shape(b)
+            if len(sa) != 2 or sa[1] != 2 or len(sb) != 2 or sb[1] != 3:
+                raise ValueError(f"scene {f}: expected pts_2d [M,2] and pts_3d [M,3], got {sa} and {sb}")
+            if sa[0] != sb[0]:
+                raise ValueError(f"scene {f}: {sa[0]} 2D points for {sb[0]} 3D points")
+            sizes.append(int(sa[0]))
+    else:
+        sizes = [int(s) for s in sizes]
+        sa, sb = _shape(pts_2d), _shape(pts_3d)
+        if len(sa) != 2 or sa[1] != 2 or len(sb) != 2 or sb[1] != 3:
+            raise ValueError(f"packed scenes: expected pts_2d [sum M,2] and pts_3d [sum M,3], got {sa} and {sb}")
+        if sa[0] != sb[0]:
+            raise ValueError(f"packed scenes: {sa[0]} 2D points for {sb[0]} 3D points")
+        if sum(sizes) != sa[0]:
+            raise ValueError(f"sizes add up to {sum(sizes)}, the packed scenes hold {sa[0]} correspondences")
+    if len(sizes) == 0:
+        raise ValueError("no scenes")
+    for f, m in enumerate(sizes):
+        if m < 4:
+            raise ValueError(f"scene {f} has {m} correspondences: a minimal set needs 4")
+    sk = _shape(K)
+    if sk != (3, 3) and sk != (len(sizes), 3, 3):
+        raise ValueError(f"K must be [3,3] or [{len(sizes)},3,3], got {sk}")
+    return sizes
+
+
+def _pick_device(device, *arrays):
+    if device is None:
+        for a in arrays:
+            for b in (a if isinstance(a, (list, tuple)) else (a,)):
+                if isinstance(b, torch.Tensor) and b.is_cuda:
+                    return b.device
+        return torch.device("cuda", torch.cuda.current_device())
+    return torch.device(device)
+
+
+def _to_dev(a, device):
+    if isinstance(a, (list, tuple)):
+        if any(isinstance(b, torch.Tensor) for b in a):
+            return torch.cat([torch.as_tensor(b, dtype=torch.float64, device=device) for b in a]).contiguous()
+        a = _np.concatenate([_np.asarray(b, dtype=_np.float64) for b in a])
+    if not isinstance(a, torch.Tensor):
+        a = torch.as_tensor(_np.ascontiguousarray(a, dtype=_np.float64))
+    return a.to(device=device, dtype=torch.float64).contiguous()
+
+
+def pack_scenes(pts_2d, pts_3d, K, sizes=None, device=None, seeds=None) -> Scenes:
+    """Validate (on the host) and pack a scene set on the device.  pts_2d / pts_3d: lists of F arrays [M_f,2] / [M_f,3], or packed
+    [sum M,2] / [sum M,3] with `sizes`, a host sequence of F ints.  K [3,3] or [F,3,3].  seeds (optional, F ints): the sampling seeds
+    travel with the offsets in one copy."""
+    sizes = _check_scenes(pts_2d, pts_3d, K, sizes)
+    F = len(sizes)
+    if seeds is not None and len(seeds) != F:
+        raise ValueError(f"{len(seeds)} seeds for {F} scenes")
+    _require_gpu()
+    device = _pick_device(device, pts_3d, pts_2d, K)
+    meta = _np.zeros(F + 1 + (F if seeds is not None else 0), dtype=_np.int64)  # offsets, then the seeds: one host-to-device copy
+    _np.cumsum(sizes, out=meta[1:F + 1])
+    if seeds is not None:
+        meta[F + 1:] = _np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=_np.uint64).view(_np.int64)
+    meta = torch.as_tensor(meta).to(device)
+    off, sd = meta[:F + 1], (meta[F + 1:] if seeds is not None else None)
+    Kd = K if isinstance(K, torch.Tensor) else torch.as_tensor(_np.ascontiguousarray(K, dtype=_np.float64))
+    return Scenes(_to_dev(pts_2d, device), _to_dev(pts_3d, device), off, sizes, _to_dev(Kd, device), sd)
+
+
+def _chk(t, name, dtype, shape, device):
+    """What the C entry points assume of a tensor: a contiguous tensor of this dtype and shape on this device."""
+    if not isinstance(t, torch.Tensor):
+        raise TypeError(f"{name}: expected a torch tensor, got {type(t).__name__}")
+    if t.device != device:
+        raise ValueError(f"{name}: on {t.device}, the scenes are on {device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name}: not contiguous")
+    return t
+
+
+def _chk_scenes(sc: Scenes):
+    dev = sc.device
+    if dev.type != "cuda":
+        raise ValueError(f"the scenes are on {dev}: cvxpnpl_amd has no CPU path")
+    _chk(sc.x, "scene pts_2d", torch.float64, (sc.total, 2), dev)
+    _chk(sc.X, "scene pts_3d", torch.float64, (sc.total, 3), dev)
+    _chk(sc.offsets, "offsets", torch.int64, (sc.F + 1,), dev)
+    _chk(sc.K, "K", torch.float64, (sc.F, 3, 3) if sc.per_scene_K else (3, 3), dev)
+
+
+def _call(sc: Scenes, name, *args):
+    with torch.cuda.device(sc.device):
+        L = _lib.ransac_lib()
+        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_last_error().decode()}")
+
+
+def _usable_mask(usable):
+    um = 0
+    for s in usable:
+        um |= 1 << int(s)
+    return um
+
+
+def sample_scenes(sc: Scenes, n_hyp: int, seeds=None, want_idx: bool = False):
+    """cvxpnpl_ransac_sample_scenes: n_hyp minimal sets per scene, scene f drawing what sample_minimal_sets(scene f, n_hyp, 4, seeds[f]) draws.
+    seeds: a sequence of F ints (None: the seeds packed with the scenes).  Returns (p2 [F*n_hyp,4,2], p3 [F*n_hyp,4,3], K_hyp [F*n_hyp,3,3] or None (shared K)) and, with
+    want_idx, idx [F*n_hyp,4] int32 (indices within the scene)."""
+    _require_gpu()
+    _chk_scenes(sc)
+    H, dev = int(n_hyp), sc.device
+    if H < 0:
+        raise ValueError("n_hyp must not be negative")
+    if seeds is None:
+        if sc.seeds is None:
+            raise ValueError("no seeds: give them here or to pack_scenes")
+        sd = sc.seeds
+    else:
+        seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
+        if len(seeds) != sc.F:
+            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
+        sd = torch.as_tensor(_np.array(seeds, dtype=_np.uint64).view(_np.int64)).to(dev)
+    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
+    n = sc.F * H
+    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
+    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
+    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
+    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
+    _call(sc, "cvxpnpl_ransac_sample_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(sc.x), _ptr(sc.X), _ptr(sc.K) if sc.per_scene_K else None,
+          _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
+
+
+def score_scenes(sc: Scenes, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
+    """cvxpnpl_ransac_score_scenes: count [F*H] int32, the inliers of hypothesis (f, h) = (R, t)[f*H + h] among scene f's correspondences."""
+    _require_gpu()
+    _chk_scenes(sc)
+    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F:
+        raise ValueError("R must be [F*H,3,3]")
+    n = R.shape[0]
+    _chk(R, "R", torch.float64, (n, 3, 3), sc.device)
+    _chk(t, "t", torch.float64, (n, 3), sc.device)
+    if status is not None:
+        _chk(status, "status", torch.int32, (n,), sc.device)
+    count = torch.empty((n,), dtype=torch.int32, device=sc.device)
+    _call(sc, "cvxpnpl_ransac_score_scenes", sc.F, n // sc.F, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable), _ptr(sc.K),
+          sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(count))
+    return count
+
+
+def select_scenes(sc: Scenes, count, R, t, status, thresh: float = 2.0):
+    """cvxpnpl_ransac_select_scenes: per scene the hypothesis of the highest count (lowest index on a tie).  Returns R [F,3,3], t [F,3],
+    head [F,4] int32 = (status, inliers, index within the scene, certified hypotheses), mask [total] uint8.  No synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F or R.shape[0] < sc.F:
+        raise ValueError("R must be [F*H,3,3] with H >= 1")
+    n, dev = R.shape[0], sc.device
+    _chk(R, "R", torch.float64, (n, 3, 3), dev)
+    _chk(t, "t", torch.float64, (n, 3), dev)
+    _chk(status, "status", torch.int32, (n,), dev)
+    _chk(count, "count", torch.int32, (n,), dev)
+    oR = torch.empty((sc.F, 3, 3), dtype=torch.float64, device=dev)
+    ot = torch.empty((sc.F, 3), dtype=torch.float64, device=dev)
+    head = torch.empty((sc.F, 4), dtype=torch.int32, device=dev)
+    mask = torch.empty((sc.total,), dtype=torch.uint8, device=dev)
+    _call(sc, "cvxpnpl_ransac_select_scenes", sc.F, n // sc.F, _ptr(sc.offsets), sc.total, _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
+          sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(oR), _ptr(ot), _ptr(head), _ptr(mask))
+    return oR, ot, head, mask
+
+
+def assemble_consensus(sc: Scenes, mask):
+    """cvxpnpl_ransac_assemble_consensus: (B27 [F,27], Q45 [F,45], count [F] int32) of every scene's masked correspondences (mask [total]
+    uint8, non-zero = taken); feed solve_cost_batch.  Fewer than three taken: NaN for that scene."""
+    _require_gpu()
+    _chk_scenes(sc)
+    dev = sc.device
+    _chk(mask, "mask", torch.uint8, (sc.total,), dev)
+    Bt = torch.empty((sc.F, 27), dtype=torch.float64, device=dev)
+    Qt = torch.empty((sc.F, 45), dtype=torch.float64, device=dev)
+    cnt = torch.empty((sc.F,), dtype=torch.int32, device=dev)
+    _call(sc, "cvxpnpl_ransac_assemble_consensus", sc.F, _ptr(sc.offsets), sc.total, _ptr(sc.x), _ptr(sc.X), _ptr(mask), _ptr(sc.K), sc.per_scene_K,
+          _ptr(Bt), _ptr(Qt), _ptr(cnt))
+    return Bt, Qt, cnt
+
+
+def refit_update_scenes(sc: Scenes, fit, fit_count, thresh, R, t, head, mask):
+    """cvxpnpl_ransac_refit_update_scenes: per scene, take the refitted pose fit.R[f] / fit.t[f] -- pose, status, mask and count together, in
+    place -- when it is usable and keeps at least head[f,1] inliers.  One launch, no synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    dev = sc.device
+    _chk(fit.R, "fit.R", torch.float64, (sc.F, 3, 3), dev)
+    _chk(fit.t, "fit.t", torch.float64, (sc.F, 3), dev)
+    _chk(fit.status, "fit.status", torch.int32, (sc.F,), dev)
+    _chk(fit_count, "fit_count", torch.int32, (sc.F,), dev)
+    _chk(R, "R", torch.float64, (sc.F, 3, 3), dev)
+    _chk(t, "t", torch.float64, (sc.F, 3), dev)
+    _chk(head, "head", torch.int32, (sc.F, 4), dev)
+    _chk(mask, "mask", torch.uint8, (sc.total,), dev)
+    _call(sc, "cvxpnpl_ransac_refit_update_scenes", sc.F, _ptr(sc.offsets), sc.total, _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count), _ptr(sc.K),
+          sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask))
+
+
+def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
+                     refit_rounds: int = 1, sizes=None, device=None, **solver_opts):
+    """Robust PnP for F scenes of different sizes in one launch sequence (what ransac_pnp does for one scene per call).
+
+    Scenes: lists of F arrays pts_2d[f] [M_f,2] / pts_3d[f] [M_f,3], or packed [sum M,2] / [sum M,3] with `sizes` (a host sequence of F
+    ints).  K [3,3] or [F,3,3].  n_hyp hypotheses are drawn PER SCENE; seed is an int (scene f uses seed + f) or a sequence of F ints, and
+    scene f draws exactly the minimal sets ransac_pnp(scene f, seed=seed_f, n_hyp=n_hyp) draws.
+    Returns a dict: R [F,3,3], t [F,3], inliers (packed bool [sum M]) and offsets [F+1] (scene f's inliers are
+    inliers[offsets[f]:offsets[f+1]]) on the device; n_inliers, status, n_certified, best_index [F] (host, columns of the one read-back
+    `head` [F,4], each row what select_best's head is for one scene); sizes, n_hyp.  One host synchronisation per call."""
+    szs = _check_scenes(pts_2d, pts_3d, K, sizes)
+    F = len(szs)
+    if seed is None:
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
+    if isinstance(seed, (int, _np.integer)):
+        seeds = [int(seed) + f for f in range(F)]
+    else:
+        seeds = [int(s) for s in seed]
+        if len(seeds) != F:
+            raise ValueError(f"{len(seeds)} seeds for {F} scenes")
+    if int(n_hyp) < 1:
+        raise ValueError("n_hyp must be at least 1")
+    sc = pack_scenes(pts_2d, pts_3d, K, sizes=szs if sizes is not None else None, device=device, seeds=seeds)
+    p2, p3, Kh = sample_scenes(sc, n_hyp)
+    # no torch kernel from here to the read-back: the F * n_hyp minimal solves in one launch sequence of the solver library ...
+    res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+    count = score_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+    R, t, head, mask = select_scenes(sc, count, res.R, res.t, res.status, thresh)
+    if refit:
+        for _ in range(max(1, int(refit_rounds))):  # ... and the F refits of the consensus sets in one solve at the cost seam
+            Bt, Qt, cnt = assemble_consensus(sc, mask)
+            fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
+            refit_update_scenes(sc, fit, cnt, thresh, R, t, head, mask)
+    h = head.cpu()   # the call's one synchronisation
+    return {"R": R, "t": t, "inliers": mask.view(torch.bool), "offsets": sc.offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3],
+            "best_index": h[:, 2], "head": h, "sizes": sc.sizes, "n_hyp": int(n_hyp)}
