@@ -308,6 +308,36 @@ __global__ void __launch_bounds__(256) calibration_copy_kernel(const char *src, 
 }
 } // namespace cvxd
 
+// Wavefront slots of a device for one instantiation of the quad kernel (one-wavefront blocks): resident blocks per CU times the CU count --
+// the blocks of a launch from this index on start when a block of the first round retires (cvxq::QuadArgs::first_round).  Asked once per
+// device and instantiation; <= 0: unknown, the kernel then gives no block a start priority.
+template <int MODE, int OCC, int LPP, bool F64SW, int VAR>
+static int quad_first_round(int dev)
+{
+#ifdef CVXQ_NO_PRIO
+    return 0;
+#else
+    static std::mutex mu;
+    static int slots[64] = {}; // 0: not asked yet, -1: the query failed
+    if (dev < 0 || dev >= 64) return 0;
+    std::lock_guard<std::mutex> g(mu);
+    if (!slots[dev]) {
+        int per_cu = 0, cus = 0;
+        const bool ok = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, cvxq::solve_quad_kernel<MODE, OCC, LPP, F64SW, VAR>, 64, 0) == hipSuccess &&
+                        hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && per_cu > 0 && cus > 0;
+        slots[dev] = ok ? per_cu * cus : -1;
+        if (!ok) (void)hipGetLastError(); // (not an error of the solve)
+    }
+    return slots[dev];
+#endif
+}
+template <int MODE, int OCC = 2, int LPP = 16, bool F64SW = false, int VAR = cvx::VAR_FULL>
+static void launch_quad(int64_t qgrid, hipStream_t s, cvxq::QuadArgs &qa, int dev)
+{
+    qa.first_round = quad_first_round<MODE, OCC, LPP, F64SW, VAR>(dev);
+    hipLaunchKernelGGL((cvxq::solve_quad_kernel<MODE, OCC, LPP, F64SW, VAR>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
+}
+
 extern "C" {
 
 void cvxpnpl_default_opts(cvxpnpl_opts_t *opts)
@@ -522,28 +552,28 @@ static int launch_solve(const BatchArgs &a, const cvxpnpl_opts_t *opts, void *st
         double *ws = wv.parked;
         const int64_t qgrid = penta ? (batch + 4) / 5 : (batch + 3) / 4;
         cvxq::QuadArgs qa;
-        qa.a = w; qa.o = o; qa.handoff_at = quad_iters; qa.qcount = count; qa.qentries = entries; qa.ws = ws;
+        qa.a = w; qa.o = o; qa.handoff_at = quad_iters; qa.qcount = count; qa.qentries = entries; qa.ws = ws; qa.first_round = 0; // (first_round: launch_quad)
 #ifdef CVXPNPL_EXPERIMENTS // 9: iterations only (tools/phase_a_time.sh); round 4, profiles/r04/tail_experiments.txt: survivors queued (layouts 11: three, 12: two wavefronts per SIMD), extras queued (13)
-        if (opts && opts->layout == 9) hipLaunchKernelGGL((cvxq::solve_quad_kernel<1, 3>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (opts && opts->layout == 11 && rc) hipLaunchKernelGGL((cvxq::solve_quad_kernel<2, 3, 16, false, cvx::VAR_RC>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (opts && opts->layout == 11) hipLaunchKernelGGL((cvxq::solve_quad_kernel<2, 3>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (opts && opts->layout == 13) hipLaunchKernelGGL((cvxq::solve_quad_kernel<3, 2>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (opts && opts->layout == 12) hipLaunchKernelGGL((cvxq::solve_quad_kernel<2, 2>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
+        if (opts && opts->layout == 9) launch_quad<1, 3>(qgrid, s, qa, cur_dev);
+        else if (opts && opts->layout == 11 && rc) launch_quad<2, 3, 16, false, cvx::VAR_RC>(qgrid, s, qa, cur_dev);
+        else if (opts && opts->layout == 11) launch_quad<2, 3>(qgrid, s, qa, cur_dev);
+        else if (opts && opts->layout == 13) launch_quad<3, 2>(qgrid, s, qa, cur_dev);
+        else if (opts && opts->layout == 12) launch_quad<2, 2>(qgrid, s, qa, cur_dev);
         else
 #endif
-        if (minimal_queued_f64) hipLaunchKernelGGL((cvxq::solve_quad_kernel<2, 2, 16, true>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
+        if (minimal_queued_f64) launch_quad<2, 2, 16, true>(qgrid, s, qa, cur_dev);
         else if (minimal_queued)
             // Four-correspondence problems: every survivor of the 24-iteration first phase goes to the queue of the launch behind this one
             // instead of being finished by its own wavefront -- 59 % of these wavefronts end with survivors, most of which are headed for
             // the interior-point path anyway, and without the wave-per-problem code the kernel runs three wavefronts per SIMD (168 registers).
             // Measured (profiles/r04/quad_mode2_minimal.txt): 50 k four-point problems 12.4 -> 13.1 M poses/s, config 5 19.8 -> 21.3 M
             // hypotheses/s (with the first attempt after 17 iterations, above: 14.9 / 24.0 M); the same schedule LOSES on the N = 10 launches, whose few survivors then start late (tail_experiments.txt).
-            hipLaunchKernelGGL((cvxq::solve_quad_kernel<2, 3>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (penta) hipLaunchKernelGGL((cvxq::solve_quad_kernel<0, 2, 12>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (rc && o.f32_sweeps_until < quad_iters) hipLaunchKernelGGL((cvxq::solve_quad_kernel<0, 2, 16, true, cvx::VAR_RC>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (rc) hipLaunchKernelGGL((cvxq::solve_quad_kernel<0, 2, 16, false, cvx::VAR_RC>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
-        else if (o.f32_sweeps_until < quad_iters) hipLaunchKernelGGL((cvxq::solve_quad_kernel<0, 2, 16, true>), dim3((unsigned)qgrid), dim3(64), 0, s, qa); // float64 sweeps (A/B mode)
-        else hipLaunchKernelGGL((cvxq::solve_quad_kernel<0, 2>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
+            launch_quad<2, 3>(qgrid, s, qa, cur_dev);
+        else if (penta) launch_quad<0, 2, 12>(qgrid, s, qa, cur_dev);
+        else if (rc && o.f32_sweeps_until < quad_iters) launch_quad<0, 2, 16, true, cvx::VAR_RC>(qgrid, s, qa, cur_dev);
+        else if (rc) launch_quad<0, 2, 16, false, cvx::VAR_RC>(qgrid, s, qa, cur_dev);
+        else if (o.f32_sweeps_until < quad_iters) launch_quad<0, 2, 16, true>(qgrid, s, qa, cur_dev); // float64 sweeps (A/B mode)
+        else launch_quad<0, 2>(qgrid, s, qa, cur_dev);
         const int64_t rgrid = batch < cvxw::RESUME_GRID_MAX ? batch : cvxw::RESUME_GRID_MAX;
         if (split) {
             // the wavefronts' own slow survivors (rescue queue) through the interior-point kernel into the resume queue, behind the planar

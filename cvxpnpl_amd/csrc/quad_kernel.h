@@ -496,7 +496,25 @@ struct QuadArgs {
     int handoff_at;
     int32_t *qcount, *qentries;
     double *ws;
+    int first_round; // wavefront slots of the device for this instantiation: blocks from here on start behind the first round (<= 0: unknown, no start priority)
 };
+
+// VALU issue priority of the wavefronts that end a launch (s_setprio; DESIGN.md section 3, profiles/r07/priority_ab.txt).  The two wavefronts
+// of a SIMD are arbitrated by priority, then age, and what one gains the other loses.  A launch lasts as long as its slowest wavefront's
+// dependent chain, and that wavefront is one that (a) started in the second round -- the younger one on its SIMD, the loser of every
+// arbitration -- and / or (b) still has a problem open after a certificate attempt, while the partner it shares the SIMD with is almost always
+// one whose finish time has slack.  So: blocks behind the first round start at CVXQ_PRIO_ROUND2, a wavefront with an open problem after an
+// attempt goes to CVXQ_PRIO_BEHIND and stays there through the hand-over and the wave-per-problem phase (it is never lowered: the wavefront
+// ends).  Both raises sit behind scalar branches -- s_setprio ignores EXEC, an unconditional one would give every wavefront the same level.
+// -DCVXQ_NO_PRIO compiles every s_setprio out (A/B builds); nothing arithmetic depends on any of this.
+#ifndef CVXQ_NO_PRIO
+#ifndef CVXQ_PRIO_ROUND2
+#define CVXQ_PRIO_ROUND2 1
+#endif
+#ifndef CVXQ_PRIO_BEHIND
+#define CVXQ_PRIO_BEHIND 2
+#endif
+#endif
 typedef const __attribute__((address_space(4))) QuadArgs *QuadArgsPtr;
 
 template <int NPW, int VAR>
@@ -546,6 +564,9 @@ __global__ void __launch_bounds__(64, OCC) solve_quad_kernel(QuadArgs k)
     // s_memrealtime: the 100 MHz reference clock, one time base for the whole device (s_memtime runs per XCD / SE)
     auto tl_now = []() { unsigned long long t; asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) : : "memory"); return t; };
     tl_[0] = tl_now();
+#endif
+#if !defined(CVXQ_NO_PRIO) && CVXQ_PRIO_ROUND2 > 0
+    if (k.first_round > 0 && __builtin_amdgcn_readfirstlane((int)blockIdx.x) >= k.first_round) __builtin_amdgcn_s_setprio(CVXQ_PRIO_ROUND2); // (scalar compare and branch)
 #endif
 
     // ---------------------------------------------------------------- roles
@@ -1205,6 +1226,10 @@ CVXQ_PH(5); /* dual fit + correction */
                 }
                 done = true;
             }
+#if !defined(CVXQ_NO_PRIO) && CVXQ_PRIO_BEHIND > 0
+            // a problem of this wavefront is still open after an attempt: from here on it is one of the wavefronts the launch waits for
+            if (__builtin_amdgcn_readfirstlane(__any(!done))) __builtin_amdgcn_s_setprio(CVXQ_PRIO_BEHIND);
+#endif
         }
 CVXQ_PH(6); /* LDL + outputs (or nothing when no check) */
         if (!done && it == o.tail_from) { // smaller penalty for the slow tail; keeps the dual: Wm scales by rho / rho_tail
