@@ -23,52 +23,11 @@
 #include "assemble_kernel.h"
 #include "synth_kernel.h"
 #include "recover_kernel.h"
+#include "launch_plan.h"
 
 namespace {
 
 using cvxb::BatchArgs; // (batch_args.h: shared with lane_kernel.hip)
-
-#ifdef CVXPNPL_EXPERIMENTS // the general scalar core on lanes: experiment builds only (layout 10) since round 5 -- see the lane branch of launch_solve
-// ---------------------------------------------------------------------------------------
-// lane-per-problem: each lane owns one problem (assembly -> ADMM -> certificate -> pose) for the first
-// handoff_at (1..5) iterations; 64 independent problems per wavefront, no cross-lane traffic, no LDS.
-// Hybrid schedule: a lane that is not finished by then parks its iterate in ws[b] and queues b for
-// resume_wave_kernel, so that one slow problem cannot hold the other 63 lanes (and the whole launch)
-// for hundreds of lane-serial iterations.
-template <bool DBL>
-__global__ void __launch_bounds__(64) solve_lane_kernel(BatchArgs a, cvx::Opts o, int handoff_at, int32_t *qcount, int32_t *qentries, double *ws)
-{
-    __shared__ double lds_const[72 * 64];
-    int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (b >= a.batch) return;
-    cvx::ProblemView pv = cvx::make_view(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem);
-    if (a.Q45) { pv.Q45 = a.Q45 + b * 45; pv.B27 = a.B27 + b * 27; }
-    cvx::Solution sol;
-    double Z[55];
-    // TWIN = false: the hand-off comes before iteration 6, where the twin-candidate logic would start.
-    // The cost matrix and the translation map (72 doubles) live in this lane's LDS column, not in registers.
-    // DBL: the eigen-solve on float64 columns (opts.f32_sweeps_until below the length of this phase; the default is packed single precision)
-    cvx::solve_problem<false, cvx::LdsStore, cvx::VAR_FULL, DBL>(pv, o, sol, a.Z ? Z : nullptr, handoff_at, ws + b * 56, cvx::LdsStore{lds_const + threadIdx.x});
-    if (sol.status == -1) {
-        const int q = atomicAdd(qcount, 1);
-        qentries[q] = (int32_t)b;
-        return;
-    }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.R[b * 9 + i] = sol.R[i];
-#pragma unroll
-    for (int i = 0; i < 3; ++i) a.t[b * 3 + i] = sol.t[i];
-    a.status[b] = sol.status;
-    if (a.iters) a.iters[b] = sol.iters;
-    if (a.cost) { a.cost[2 * b] = sol.cost; a.cost[2 * b + 1] = sol.dobj; }
-    if (a.work) { a.work[2 * b] = sol.rank; a.work[2 * b + 1] = sol.sweeps; }
-    if (a.Z) {
-#pragma unroll
-        for (int i = 0; i < 55; ++i) a.Z[b * 55 + i] = Z[i];
-    }
-}
-
-#endif // CVXPNPL_EXPERIMENTS
 
 // (solve_lane2_kernel, the first phase of the lane-hybrid schedule: lane_kernel.hip, a translation unit of its own -- cvxb::launch_lane2)
 
@@ -271,26 +230,6 @@ int set_err(const char *what, hipError_t e)
     return -2;
 }
 
-cvx::Opts to_core(const cvxpnpl_opts_t *opts)
-{
-    cvx::Opts o = cvx::default_opts();
-    if (opts) {
-        o.eps = opts->eps; o.max_iters = opts->max_iters; o.rho = opts->rho; o.alpha = opts->alpha;
-        o.first_check = opts->first_check; o.check_every = opts->check_every; o.res_tol = opts->res_tol;
-        o.jacobi_sweeps = opts->jacobi_sweeps; o.jacobi_tol = opts->jacobi_tol; o.warm_start = opts->warm_start; o.rho_tail = opts->rho_tail; o.tail_from = opts->tail_from;
-        o.variant = opts->variant;
-        o.adapt_every = opts->adapt_every; o.adapt_from = opts->adapt_from; o.adapt_mu = opts->adapt_mu; o.adapt_tau = opts->adapt_tau;
-        o.stall_from = opts->stall_from; o.stall_lam = opts->stall_lam; o.stall_res = opts->stall_res; o.stall_drop = opts->stall_drop;
-        o.rescue_from = opts->rescue_from;
-        o.f32_sweeps_until = opts->f32_sweeps_until;
-        o.sweep_schedule = opts->sweep_schedule != 0;
-        o.dual_shift = opts->dual_shift < 0.0 ? (opts->variant == CVXPNPL_VARIANT_RC ? 0.006 : cvx::DUAL_SHIFT_DEFAULT) : opts->dual_shift; // (rc, 50 k problems: 17.3 M poses/s without, 17.3 / 18.4 / 18.3 M with 0.015 / 0.006 / 0.001)
-        o.dual_refine = opts->dual_refine != 0;
-    }
-    if (o.f32_sweeps_until < 0) o.f32_sweeps_until = cvx::F32_SWEEPS_DEFAULT;
-    return o;
-}
-
 } // namespace
 
 // diagnostics: a copy with W bytes per lane and a known byte count, against which bench.py calibrates rocprofv3's
@@ -340,21 +279,7 @@ static void launch_quad(int64_t qgrid, hipStream_t s, cvxq::QuadArgs &qa, int de
 
 extern "C" {
 
-void cvxpnpl_default_opts(cvxpnpl_opts_t *opts)
-{
-    cvx::Opts o = cvx::default_opts();
-    opts->eps = o.eps; opts->max_iters = o.max_iters; opts->rho = o.rho; opts->alpha = o.alpha;
-    opts->first_check = 0 /* by layout, see cvxpnpl_amd.h */; opts->check_every = o.check_every; opts->res_tol = o.res_tol;
-    opts->jacobi_sweeps = o.jacobi_sweeps; opts->jacobi_tol = o.jacobi_tol; opts->warm_start = o.warm_start; opts->rho_tail = o.rho_tail; opts->tail_from = o.tail_from; opts->lane_iters = -1; opts->layout = CVXPNPL_LAYOUT_AUTO; opts->variant = CVXPNPL_VARIANT_FULL;
-    opts->adapt_every = o.adapt_every; opts->adapt_from = o.adapt_from; opts->adapt_mu = o.adapt_mu; opts->adapt_tau = o.adapt_tau;
-    opts->stall_from = o.stall_from; opts->stall_lam = o.stall_lam; opts->stall_res = o.stall_res; opts->stall_drop = o.stall_drop;
-    opts->rescue_from = o.rescue_from;
-    opts->f32_sweeps_until = -1;
-    opts->sweep_schedule = 1;
-    opts->dual_shift = -1.0; /* by variant */
-    opts->dual_refine = -1;
-    opts->struct_size = (uint32_t)sizeof(cvxpnpl_opts_t);
-}
+void cvxpnpl_default_opts(cvxpnpl_opts_t *opts) { cvxplan::public_defaults(opts); }
 
 size_t cvxpnpl_opts_size(void) { return sizeof(cvxpnpl_opts_t); }
 
@@ -370,252 +295,55 @@ static int check_args(int64_t batch, int32_t n_p, const double *p2, const double
     return 0;
 }
 
-// the launches of one solve: layout policy + kernels (shared by the correspondence entry and the cost entry)
+// the launches of one solve (shared by the correspondence entry and the cost entry): the policy is cvxplan::plan_solve (launch_plan.h),
+// this function executes what it decided
 static int launch_solve(const BatchArgs &a, const cvxpnpl_opts_t *opts, void *stream)
 {
+    static constexpr cvxplan::Limits limits = {cvxw::RS_LANE, cvxw::RS_FULL, cvxw::RESUME_GRID_MAX, cvxi::IPMQ_GRID_MAX, cvxw::WPB};
     const int64_t batch = a.batch;
     if (!a.R || !a.t || !a.status) { snprintf(g_err, sizeof(g_err), "cvxpnpl: R, t and status outputs are required"); return -1; }
-    if (opts && opts->struct_size != (uint32_t)sizeof(cvxpnpl_opts_t)) {
-        // a caller built against another revision of cvxpnpl_opts_t: refuse rather than read fields that are not there
-        snprintf(g_err, sizeof(g_err), "cvxpnpl: options block of %u bytes, this library's cvxpnpl_opts_t has %zu (cvxpnpl_default_opts / cvxpnpl_opts_size)",
-                 opts->struct_size, sizeof(cvxpnpl_opts_t));
-        return -1;
-    }
-    if (opts && (opts->max_iters < 1 || opts->f32_sweeps_until < -1 || opts->f32_sweeps_until > cvx::F32_SWEEPS_DEFAULT || !(opts->rho > 0) || !(opts->eps > 0) || opts->check_every < 1 || opts->first_check < 0 ||
-                 (opts->variant != CVXPNPL_VARIANT_FULL && opts->variant != CVXPNPL_VARIANT_RC) || opts->adapt_every < 0 ||
-                 (opts->adapt_every > 0 && !(opts->adapt_mu >= 1.0 && opts->adapt_tau > 1.0)) || opts->rescue_from < -1 || !((opts->dual_shift >= 0.0 && opts->dual_shift <= 1.0) || opts->dual_shift == -1.0) || opts->dual_refine < -1 || opts->dual_refine > 1)) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl: bad options");
-        return -1;
-    }
-    // layouts: the public enum only.  The experiment layouts of rounds 2-4 (9: quad iterations only at three wavefronts per SIMD, 10: the lane
-    // schedule on the general scalar core, 11-13: the tail experiments of profiles/r04/tail_experiments.txt) exist in experiment builds
-    // (-DCVXPNPL_EXPERIMENTS, tools/experiments/build_experiments.sh) and nowhere else
-#ifdef CVXPNPL_EXPERIMENTS
-    const bool layout_known = !opts || (opts->layout >= CVXPNPL_LAYOUT_AUTO && opts->layout <= CVXPNPL_LAYOUT_PENTA) || (opts->layout >= 9 && opts->layout <= 13);
-#else
-    const bool layout_known = !opts || (opts->layout >= CVXPNPL_LAYOUT_AUTO && opts->layout <= CVXPNPL_LAYOUT_PENTA);
-#endif
-    if (!layout_known) { snprintf(g_err, sizeof(g_err), "cvxpnpl: bad options (layout %d is not one of CVXPNPL_LAYOUT_*)", opts->layout); return -1; }
-    cvx::Opts o = to_core(opts);
-    if (!opts) o.first_check = 0; // (by layout, below)
+    if (!cvxplan::validate(opts, g_err, sizeof(g_err))) return -1;
+    const cvxplan::SolvePlan p = cvxplan::plan_solve(batch, a.n_p, a.n_l, a.Q45 != nullptr, opts, limits);
+    if (p.too_large) { snprintf(g_err, sizeof(g_err), "cvxpnpl: batch too large for one launch"); return -1; }
     int cur_dev = 0;
     if (hipGetDevice(&cur_dev) != hipSuccess) { snprintf(g_err, sizeof(g_err), "cvxpnpl: hipGetDevice failed"); return -2; }
     std::lock_guard<std::mutex> launch_lock(launch_mutex(cur_dev, stream)); // (see launch_mutex)
     hipStream_t s = (hipStream_t)stream;
-    const int block = 64;
-    int64_t grid = (batch + block - 1) / block;
-    if (grid > 0x7fffffffLL) { snprintf(g_err, sizeof(g_err), "cvxpnpl: batch too large for one launch"); return -1; }
-    int layout = opts ? opts->layout : CVXPNPL_LAYOUT_AUTO;
-    // AUTO, by launch size (measured on one MI355X, M poses/s, PnP N = 10, one launch stream; wave / quad: profiles/r02/layout_sweep.txt,
-    // quad / lane-hybrid with the register-budgeted first phase: profiles/r03/layout_sweep2.txt, two problem sets per size):
-    //   wave / quad      2 k: 19.7 / 17.3    5 k: 27.9 / 34.1    10 k: 33.8 / 51.7
-    //   quad / lane     10 k: 51.6, 49.1 / 36.7, 41.0    16 k: 52.0, 73.5 / 48.7, 63.3    20 k: 74.5, 72.8 / 79.6, 73.4
-    //                   24 k: 74.5, 75.6 / 95.4, 86.8    32 k: 87.2, 87.7 / 115.0, 124.8   125 k: 113 / 247
-    // * below 2560 problems a wavefront per problem: every SIMD gets work and a finished problem frees its slot at once;
-    // * from there four problems per wavefront (one per DPP row): 2.5x fewer instructions per problem;
-    // * from 20 000 the lane-hybrid schedule (64 problems per wavefront for the first lane_iters iterations): fewest instructions
-    //   per problem, but it needs ~20 k problems to give every SIMD a wavefront (round 2, general scalar core: crossover 24 576).
-    //   (with every sweep in float64 the crossover is the same: quad / lane 16 k: 58.0 / 57.0, 20 k: 59.0 / 59.6, 24 k: 62.2 / 75.9, 32 k: 67.9 / 99.0 -- profiles/r04/f64_layout_crossover.txt)
-    // The problems the quad phase leaves open are finished by the same wavefront, those of the lane phase by a second kernel,
-    // one per wavefront in both cases.
-    // Minimal problems (four correspondences; the cost seam does not say): 18 iterations on average and a fifth of them beyond 32 --
-    // the lane-hybrid schedule would park nearly all of them for the one-problem-per-wavefront phase.  They stay four per wavefront
-    // for 24 iterations instead (first attempt after 7 -- round 4: 17, and their survivors are queued: minimal_queued below), like the rc variant: 50 k problems 11.2 -> 12.4 M poses/s (lane_iters 16 / 24 /
-    // 32 / 40: 12.1 / 12.4 / 11.7-12.2 / 12.3; five correspondences and more: the lane-hybrid schedule wins, 36.8 against 33.6 M at N = 5).
-#ifdef CVXPNPL_EXPERIMENTS
-    const bool layout_auto_like = layout == CVXPNPL_LAYOUT_AUTO || layout == 11 || layout == 12 || layout == 13;
-#else
-    const bool layout_auto_like = layout == CVXPNPL_LAYOUT_AUTO;
-#endif
-#ifdef CVXPNPL_EXPERIMENTS // (tuning builds: opts.lane_iters sets the length of the first phase of four-point problems)
-    const bool minimal = !a.Q45 && a.n_p + a.n_l <= 4 && o.variant == cvx::VAR_FULL && layout_auto_like && batch >= 2560 && o.max_iters > 24;
-#else
-    const bool minimal = !a.Q45 && a.n_p + a.n_l <= 4 && o.variant == cvx::VAR_FULL && layout_auto_like && batch >= 2560 && o.max_iters > 24 &&
-                         (!opts || opts->lane_iters <= 0);
-#endif
-    if (layout == CVXPNPL_LAYOUT_AUTO) layout = batch < 2560 ? CVXPNPL_LAYOUT_WAVE : ((batch < 20000 || minimal) ? CVXPNPL_LAYOUT_QUAD : CVXPNPL_LAYOUT_LANE);
-    // The 16-equality variant (benchmarks/toolkit/methods/rc.py): wave-per-problem and, since round 3, the quad schedule (the
-    // constraint set is a template parameter of the kernels); the lane kernels and the interior-point path are built for the full set.
-    const bool rc = o.variant == cvx::VAR_RC;
-    if (rc && (layout == CVXPNPL_LAYOUT_LANE || layout == CVXPNPL_LAYOUT_PENTA || layout == 9 || layout == 10 || layout == 12 || layout == 13)) layout = CVXPNPL_LAYOUT_QUAD; // (9-13: experiment builds only)
+    g_last_layout = p.last_layout;
+    // ONE workspace view per solve: a second fetch with a larger stride may free and reallocate the buffer, and queue pointers taken
+    // from the first would dangle
+    WsView wv = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (p.needs_workspace && !get_workspace(batch, p.ws_stride, stream, wv)) return -2;
+    const cvx::Opts &o = p.o;
     cvxw::WaveArgs w;
     w.batch = batch; w.n_p = a.n_p; w.n_l = a.n_l; w.K_per_problem = a.K_per_problem;
     w.p2 = a.p2; w.p3 = a.p3; w.l2 = a.l2; w.l3 = a.l3; w.K = a.K;
     w.R = a.R; w.t = a.t; w.cost = a.cost; w.Z = a.Z; w.status = a.status; w.iters = a.iters; w.work = a.work;
     w.Q45 = a.Q45; w.B27 = a.B27;
-    w.rq_count = nullptr; w.rq_entries = nullptr;
-    int quad_iters = opts ? opts->lane_iters : -1;
-    // rc: the weaker relaxation certifies after ~21 iterations instead of 5 (N = 10): a longer first phase, first attempt later
-    if (quad_iters <= 0 && rc) quad_iters = 36; // (profiles/r03/rc_tune.txt: 28 / 36 / 44 within 1 %)
-    if (quad_iters <= 0 && minimal) quad_iters = 24;
-    if (quad_iters <= 0) quad_iters = 7; // measured (4 problem sets at 10 k, same box): 5: 0.242 ms, 7: 0.233, 8: 0.235, 10: 0.240; 24 k: 7 = 10 (round 1, second phase as a call: 8-12)
-    if (quad_iters > 48) quad_iters = 48; // (rc: up to 48 -- still inside the wave kernel's own single-precision window of 64)
-    if (quad_iters > 16 && !rc && !minimal) quad_iters = 16; // (a caller's lane_iters: the quad phase is the YOUNG part of a solve, its slow survivors belong to the wave-per-problem phase.
-    // Minimal problems and the rc variant run 24 / 36-48 iterations here, in single-precision sweeps by default -- inside the window of 64 that
-    // opts.f32_sweeps_until allows and the host experiment covers; device A/B against float64 sweeps: profiles/r04/f32_phase_ab.txt)
-#ifdef CVXPNPL_EXPERIMENTS
-    const bool lane_general = layout == 10; // experiment / A-B (tools/README.md): the lane schedule with the general scalar core (solve_lane_kernel)
-    if (lane_general) layout = CVXPNPL_LAYOUT_LANE;
-#else
-    const bool lane_general = false;
-#endif
-    // the REQUEST (five problems per wavefront) and the kernel that serves it are separate: with float64 sweeps the twelve-lane geometry
-    // does not exist and the request runs the sixteen-lane quad kernel -- either way the layout from here on is QUAD (round-3 advisor:
-    // a PENTA request with f32_sweeps_until = 0 used to fall through to the lane branch with a workspace fetched for another stride)
-    const bool penta_req = layout == CVXPNPL_LAYOUT_PENTA;
-    const bool penta = penta_req && !(o.f32_sweeps_until < quad_iters); // (float64 sweeps: built for the sixteen-lane geometry only)
-    if (layout == 9 || layout == 11 || layout == 12 || layout == 13 || penta_req) layout = CVXPNPL_LAYOUT_QUAD; // (9: experiment (tools/README.md): quad iterations only, 3 waves/SIMD, solve_quad_kernel<1>)
-    // The register-budgeted lane kernel (lane_core.h) covers the schedule of the defaults: one attempt, right at the hand-off point, warm-started
-    // eigen-solves.  Any other combination of options (first_check != lane_iters, warm_start = 0) used to fall through to the general scalar
-    // core on lanes (solve_lane_kernel: 1 008-1 014 spilled registers, 2.2-2.7 KB of scratch per lane, a third of the speed) without saying
-    // so; round 5 sent such a request to the wave-per-problem layout -- one problem per wavefront, also at 125 000 problems, and with the
-    // attempt schedule already derived for the lane layout (advisor).  Now the layout is settled HERE, before anything is derived from it:
-    // a lane request the budgeted kernel cannot serve runs the next-best schedule for its size (quad from 2 560 problems, wave below), the
-    // first attempt then follows THAT layout's default, and cvxpnpl_last_layout() says what ran.
-    int lane_iters = opts ? opts->lane_iters : -1;
-    {
-        const int fc_lane = o.first_check > 0 ? o.first_check : 6;
-        if (lane_iters <= 0) lane_iters = fc_lane;
-        if (lane_iters > 6) lane_iters = 6; // (see the lane branch below)
-#ifndef CVXPNPL_EXPERIMENTS
-        const bool budgeted = !lane_general && fc_lane == lane_iters && lane_iters >= 2 && o.warm_start != 0;
-        if (layout == CVXPNPL_LAYOUT_LANE && !budgeted) {
-            layout = batch >= 2560 ? CVXPNPL_LAYOUT_QUAD : CVXPNPL_LAYOUT_WAVE;
-            quad_iters = 7; // (the caller's lane_iters was meant for the lane phase)
-        }
-#endif
+    w.rq_count = p.rescue ? wv.rq_count : nullptr; w.rq_entries = p.rescue ? wv.rq_entries : nullptr; // the interior-point path's queue
+    w.rq_ws = p.split ? wv.parked : nullptr; w.rq_stride = p.split ? p.ws_stride : 0;
+    cvxq::QuadArgs qa;
+    qa.a = w; qa.o = o; qa.handoff_at = p.handoff_at; qa.qcount = wv.count; qa.qentries = wv.entries; qa.ws = wv.parked; qa.first_round = 0; // (first_round: launch_quad)
+    switch (p.first) {
+    case cvxplan::K_WAVE_FULL: case cvxplan::K_WAVE_RC: launch_wave(p.first_grid, s, w, o); break; // (by o.variant)
+    case cvxplan::K_LANE2_F32: case cvxplan::K_LANE2_F64:
+        cvxb::launch_lane2(p.first == cvxplan::K_LANE2_F64, (unsigned)p.first_grid, 64u, (void *)s, a, o, p.handoff_at, wv.count, wv.entries, wv.parked);
+        break;
+    case cvxplan::K_QUAD_MINIMAL_F64: launch_quad<2, 2, 16, true>(p.first_grid, s, qa, cur_dev); break;
+    case cvxplan::K_QUAD_MINIMAL: launch_quad<2, 3>(p.first_grid, s, qa, cur_dev); break;
+    case cvxplan::K_QUAD_PENTA: launch_quad<0, 2, 12>(p.first_grid, s, qa, cur_dev); break;
+    case cvxplan::K_QUAD_RC_F64: launch_quad<0, 2, 16, true, cvx::VAR_RC>(p.first_grid, s, qa, cur_dev); break;
+    case cvxplan::K_QUAD_RC: launch_quad<0, 2, 16, false, cvx::VAR_RC>(p.first_grid, s, qa, cur_dev); break;
+    case cvxplan::K_QUAD_F64: launch_quad<0, 2, 16, true>(p.first_grid, s, qa, cur_dev); break;
+    case cvxplan::K_QUAD: launch_quad<0, 2>(p.first_grid, s, qa, cur_dev); break;
     }
-    if (layout == CVXPNPL_LAYOUT_QUAD && !(quad_iters >= 1 && o.max_iters > quad_iters)) layout = CVXPNPL_LAYOUT_WAVE;
-    // (rc with float64 sweeps: solve_quad_kernel<0, 2, 16, true, VAR_RC> since round 5 -- until then such a request ran the wave layout)
-    // First certificate attempt (0 = by layout): after 5 iterations 94 % of N = 10 problems certify, after 6 99 %.  In the lane-hybrid
-    // schedule every problem that fails the first attempt is parked and resumed one per wavefront, so the later attempt pays for its
-    // extra iteration: 125 k problems 157 -> 164 M poses/s, PnPL 100 k 116 -> 126 M.  The quad and wave layouts keep 5 (quad with 6, launch
-    // time relative to 5 over 4 problem sets per size: 3 k 0.93, 5 k 1.07, 8 k 1.02, 10 k 0.98, 12 k 1.07, 16 k 1.03, 20 k 1.02, 24 k 0.97;
-    // wave: -12 % at 2 k).
-    // Four-correspondence problems in the schedule that queues its survivors (below): an attempt costs the whole wavefront two to three
-    // iterations' worth -- at three wavefronts per SIMD the certificate's code is the part that spills -- and these problems need 14-20
-    // iterations on average: first attempt after 17 (profiles/r04/minimal_tune*.txt, 50 k problems / config 5, M per second: first attempt
-    // after 7: 13.0 / 21.3, 9: 13.5 / 22.4, 13: 14.5 / 23.5, 17: 14.9 / 24.0, 21: 14.5 / 23.9; every third iteration instead of every second: same).
-    // (round 5: in both precision modes -- with float64 sweeps the kernel keeps two wavefronts per SIMD, solve_quad_kernel<2, 2, 16, true>)
-    const bool minimal_queued = minimal && layout == CVXPNPL_LAYOUT_QUAD;
-    const bool minimal_queued_f64 = minimal_queued && o.f32_sweeps_until < quad_iters;
-    // (rc in the quad schedule: 19 instead of 11 -- profiles/r04/rc_tune_r04.txt: 50 k problems 18.3 -> 19.3 M poses/s, 10 k 9.0 -> 9.3 M; the same effect, smaller)
-    if (o.first_check <= 0) o.first_check = rc ? (layout == CVXPNPL_LAYOUT_QUAD ? 19 : 11) : (minimal_queued ? 17 : (minimal ? 7 : (layout == CVXPNPL_LAYOUT_LANE ? 6 : 5))); // (rc: nothing certifies before ~10 iterations; 5 ... 15 within 3 %)
-    // interior-point path for the problems still open after rescue_from iterations (ipm_wave.h): its queue lives in the workspace
-    // -1 (default): by problem size.  Slow convergence is a property of minimal and near-minimal configurations
-    // (profiles/r02/remaining_iters.jsonl, 100 k problems each, first-order iterations only: with N = 4 / 5 / 6 / 7 correspondences
-    // 21 % / 3.8 % / 0.7 % / 0.14 % of the problems are still open after 32 iterations and 27 % / 17 % / 12 % / 6 % of those need more
-    // than the ~75 iterations an interior-point solve costs, slowest 1 455 / 1 037 / 581 / 227; with N = 8 the slowest takes 99, with
-    // N = 10 (1 M problems) 61, and a problem that is open after 48 finishes within the next 3-25).  A threshold below the natural tail
-    // of a workload sends problems through a 0.3 ms solve they did not need and ends the launch later: 100 k problems with N = 8
-    // 1.05 ms without the path, 1.35 ms with 96; 1 M with N = 10 4.46 / 4.75 ms with 96 / 32; against that 10 k problems with N = 4
-    // 4.77 / 1.78 ms, N = 6 (100 k) 3.42 / 1.91 ms without / with 32, N = 7 (100 k) 1.71 / 1.49 ms without / with 64.
-    if (o.rescue_from < 0) {
-        const int n = a.Q45 ? 8 : a.n_p + a.n_l;
-        o.rescue_from = n <= 6 ? 32 : (n == 7 ? 64 : 128);
-        // rc: the weaker relaxation is tight less often, and a problem whose relaxation is not tight crawls to max_iters -- 13 of 10 000
-        // N = 10 problems run all 2 500 iterations, 10 ms per launch whatever the layout (profiles/r03/rc_rate.txt) -- while the
-        // typical problem certifies after ~19 iterations (median; p90 33): hand over at 48 whatever the size
-        if (rc) o.rescue_from = 48; // (profiles/r03/rc_tune.txt, 50 k problems: 48 / 64 / 80 / 96 -> 2.92 / 3.10 / 3.46 / 3.63 ms, same outcomes)
+    for (int i = 0; i < p.n_follow; ++i) {
+        const cvxplan::FollowUp &f = p.follow[i];
+        if (f.kind == cvxplan::F_IPM) launch_ipm(batch, s, w, o, wv.count, wv.entries);
+        else if (f.kind == cvxplan::F_RESUME) launch_resume(f.grid, s, w, o, wv.count, wv.entries, wv.parked, f.full);
+        else if (f.two_queues) launch_rescue(batch, s, w, o, wv.count, wv.entries, wv.parked); // (both queues in one launch)
+        else launch_rescue(batch, s, w, o);
     }
-    const bool rescue = o.rescue_from > 0 && o.max_iters > o.rescue_from;
-    // ONE workspace view per solve, fetched after the layout is settled and with the stride of the schedule that will run: a second
-    // fetch with a larger stride may free and reallocate the buffer, and queue pointers taken from the first would dangle
-    // (lane_iters and the budgeted / not budgeted decision: above, where the layout is settled)
-    const bool lane_budgeted = !lane_general && o.first_check == lane_iters && lane_iters >= 2 && o.warm_start != 0;
-    g_last_layout = (layout == CVXPNPL_LAYOUT_QUAD && penta) ? CVXPNPL_LAYOUT_PENTA : layout;
-    const bool lane_hybrid = layout == CVXPNPL_LAYOUT_LANE && o.max_iters > lane_iters;
-    // The interior-point path comes in two builds.  Fused (cvxw::rescue_wave_kernel: the solve compiled into a resume kernel, one launch
-    // behind the first kernel) where it is a safety net -- seven correspondences and more: its queue is empty in nearly every launch and
-    // one more (empty) launch would cost the 10 k-problem step 2 %.  Split (cvxw::ipm_wave_kernel + the plain resume kernel) where
-    // problems really go through it -- at most six correspondences, the 16-equality variant: a fifth of the four-point problems.
-#ifndef CVXPNPL_FUSED_IPM
-    const bool split = rescue && (rc || (!a.Q45 && a.n_p + a.n_l <= 5)); // (measured, split / fused, M poses/s: N = 4 50 k 17.96 / 15.07, config 5 25.6 / 24.7, N = 5 100 k 37.3 / 35.8, N = 6 125 k 73.1 / 75.5: profiles/r05/ipm_quad_ab.txt)
-#else
-    const bool split = false; // (A/B builds: every workload through the fused kernel, as until round 4)
-#endif
-    WsView wv = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    const int ws_stride = layout == CVXPNPL_LAYOUT_QUAD ? cvxw::RS_FULL : ((lane_hybrid || split) ? cvxw::RS_LANE : 0);
-    if (rescue || layout == CVXPNPL_LAYOUT_QUAD || lane_hybrid) {
-        if (!get_workspace(batch, ws_stride, stream, wv)) return -2;
-    }
-    w.rq_ws = nullptr; w.rq_stride = 0;
-    if (rescue) { w.rq_count = wv.rq_count; w.rq_entries = wv.rq_entries; }
-    if (split) { w.rq_ws = wv.parked; w.rq_stride = ws_stride; }
-    const int64_t rgrid_all = batch < cvxw::RESUME_GRID_MAX ? batch : cvxw::RESUME_GRID_MAX;
-    if (layout == CVXPNPL_LAYOUT_QUAD) {
-        // four problems per wavefront for the first quad_iters iterations, survivors resumed one per wavefront
-        // (a wavefront finishes its own survivors; only planar scenes, recognised before the first iteration,
-        // are queued for the resume kernel behind it -- an empty queue costs that launch a few microseconds.
-        // The resume kernel leaves the queue counter at zero for the next launch: no memset per call.)
-        int32_t *count = wv.count, *entries = wv.entries;
-        double *ws = wv.parked;
-        const int64_t qgrid = penta ? (batch + 4) / 5 : (batch + 3) / 4;
-        cvxq::QuadArgs qa;
-        qa.a = w; qa.o = o; qa.handoff_at = quad_iters; qa.qcount = count; qa.qentries = entries; qa.ws = ws; qa.first_round = 0; // (first_round: launch_quad)
-#ifdef CVXPNPL_EXPERIMENTS // 9: iterations only (tools/phase_a_time.sh); round 4, profiles/r04/tail_experiments.txt: survivors queued (layouts 11: three, 12: two wavefronts per SIMD), extras queued (13)
-        if (opts && opts->layout == 9) launch_quad<1, 3>(qgrid, s, qa, cur_dev);
-        else if (opts && opts->layout == 11 && rc) launch_quad<2, 3, 16, false, cvx::VAR_RC>(qgrid, s, qa, cur_dev);
-        else if (opts && opts->layout == 11) launch_quad<2, 3>(qgrid, s, qa, cur_dev);
-        else if (opts && opts->layout == 13) launch_quad<3, 2>(qgrid, s, qa, cur_dev);
-        else if (opts && opts->layout == 12) launch_quad<2, 2>(qgrid, s, qa, cur_dev);
-        else
-#endif
-        if (minimal_queued_f64) launch_quad<2, 2, 16, true>(qgrid, s, qa, cur_dev);
-        else if (minimal_queued)
-            // Four-correspondence problems: every survivor of the 24-iteration first phase goes to the queue of the launch behind this one
-            // instead of being finished by its own wavefront -- 59 % of these wavefronts end with survivors, most of which are headed for
-            // the interior-point path anyway, and without the wave-per-problem code the kernel runs three wavefronts per SIMD (168 registers).
-            // Measured (profiles/r04/quad_mode2_minimal.txt): 50 k four-point problems 12.4 -> 13.1 M poses/s, config 5 19.8 -> 21.3 M
-            // hypotheses/s (with the first attempt after 17 iterations, above: 14.9 / 24.0 M); the same schedule LOSES on the N = 10 launches, whose few survivors then start late (tail_experiments.txt).
-            launch_quad<2, 3>(qgrid, s, qa, cur_dev);
-        else if (penta) launch_quad<0, 2, 12>(qgrid, s, qa, cur_dev);
-        else if (rc && o.f32_sweeps_until < quad_iters) launch_quad<0, 2, 16, true, cvx::VAR_RC>(qgrid, s, qa, cur_dev);
-        else if (rc) launch_quad<0, 2, 16, false, cvx::VAR_RC>(qgrid, s, qa, cur_dev);
-        else if (o.f32_sweeps_until < quad_iters) launch_quad<0, 2, 16, true>(qgrid, s, qa, cur_dev); // float64 sweeps (A/B mode)
-        else launch_quad<0, 2>(qgrid, s, qa, cur_dev);
-        const int64_t rgrid = batch < cvxw::RESUME_GRID_MAX ? batch : cvxw::RESUME_GRID_MAX;
-        if (split) {
-            // the wavefronts' own slow survivors (rescue queue) through the interior-point kernel into the resume queue, behind the planar
-            // scenes parked there; a parked problem that reaches rescue_from in the resume kernel takes the second round
-            for (int round = 0; round < 2; ++round) {
-                launch_ipm(batch, s, w, o, count, entries);
-                launch_resume(rgrid, s, w, o, count, entries, ws, true);
-            }
-        } else if (rescue) launch_rescue(batch, s, w, o, count, entries, ws); // (both queues in one launch)
-        else launch_resume(rgrid, s, w, o, count, entries, ws, true);
-    } else if (layout == CVXPNPL_LAYOUT_WAVE) {
-        int64_t wgrid = (batch + cvxw::WPB - 1) / cvxw::WPB;
-        if (wgrid > 0x7fffffffLL) { snprintf(g_err, sizeof(g_err), "cvxpnpl: batch too large for one launch"); return -1; }
-        launch_wave(wgrid, s, w, o);
-    } else {
-        // hand-off point of the hybrid schedule (<= 0: default): right after the first certificate attempt (opts.first_check: 6
-        // by default in this layout) -- later is slower (round 1, first attempt at 5: hand-off at 5 / 6 / 7: 110 / 105 / 100 M at 125 k).
-        // (lane_iters: above.)  The lane phase never runs past 6 iterations: from then on the few problems still open are the
-        // slow / ambiguous ones (twin candidates, tails), which belong to the wave-per-problem kernel -- one of
-        // them would hold 63 idle lanes, so the lane kernel is built without that logic.
-        if (lane_hybrid) {
-            // hybrid: lanes for the first lane_iters iterations, survivors resumed one per wavefront
-            int32_t *count = wv.count, *entries = wv.entries;
-            double *ws = wv.parked;
-            const bool budgeted = lane_budgeted;
-            if (budgeted) cvxb::launch_lane2(!(o.f32_sweeps_until >= lane_iters), (unsigned)grid, (unsigned)block, (void *)s, a, o, lane_iters, count, entries, ws); // (true: float64 sweeps)
-#ifdef CVXPNPL_EXPERIMENTS
-            else if (o.f32_sweeps_until < lane_iters) hipLaunchKernelGGL(solve_lane_kernel<true>, dim3((unsigned)grid), dim3(block), 0, s, a, o, lane_iters, count, entries, ws); // float64 sweeps (A/B mode)
-            else hipLaunchKernelGGL(solve_lane_kernel<false>, dim3((unsigned)grid), dim3(block), 0, s, a, o, lane_iters, count, entries, ws);
-#endif
-            const int64_t rgrid = batch < cvxw::RESUME_GRID_MAX ? batch : cvxw::RESUME_GRID_MAX;
-            launch_resume(rgrid, s, w, o, count, entries, ws, false);
-        } else {
-            // fewer iterations allowed than the lane phase would run: the wave kernel does the whole solve
-            int64_t wgrid = (batch + cvxw::WPB - 1) / cvxw::WPB;
-            launch_wave(wgrid, s, w, o);
-        }
-    }
-    if (split && layout != CVXPNPL_LAYOUT_QUAD) {
-        launch_ipm(batch, s, w, o, wv.count, wv.entries);
-        launch_resume(rgrid_all, s, w, o, wv.count, wv.entries, wv.parked, false);
-    } else if (rescue && layout != CVXPNPL_LAYOUT_QUAD) launch_rescue(batch, s, w, o);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_err("solve kernel launch", e);
     return 0;

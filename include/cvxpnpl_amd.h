@@ -38,7 +38,8 @@ enum {
     CVXPNPL_REFLECTION = 4   /* uncertified and det(U V^T) < 0; returned as is, like the reference (:510-511) */
 };
 
-/* kernel layouts (A/B switch; all produce the same results).  Any other value of opts.layout is refused ("bad options", -1). */
+/* kernel layouts (A/B switch; all produce the same results).  Any other value of opts.layout is refused ("bad options", -1): the
+   experiment layouts 9-13 of earlier revisions are records under profiles/ now, no build of the library has them. */
 enum {
     CVXPNPL_LAYOUT_AUTO = 0, /* by launch size: wave below 2560 problems, quad below 20000, lane (hybrid) from there; four-correspondence
                                 problems: quad from 2560 on, with a 24-iteration first phase and the first attempt after 7 */

@@ -27,6 +27,7 @@ def build(force=False):
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off",
                                "-o", _SO, srcs[0]])
+    build_plan()
     return _SO
 
 
@@ -40,6 +41,26 @@ def lib():
             build()
             _lib = C.CDLL(_SO)
     return _lib
+
+
+_PLAN_SO = os.path.join(_HERE, "libplanshim.so")
+_plan_lib = None
+
+
+def build_plan():
+    """plan_shim.cpp: the launch policy of the solver (csrc/launch_plan.h, a host-only header) behind a C entry"""
+    srcs = [os.path.join(_HERE, "plan_shim.cpp"), os.path.join(_CSRC, "launch_plan.h"), os.path.join(_CSRC, "solver_core.h"),
+            os.path.join(os.path.dirname(_CSRC), os.pardir, "include", "cvxpnpl_amd.h")]
+    if not os.path.exists(_PLAN_SO) or os.path.getmtime(_PLAN_SO) < max(os.path.getmtime(s) for s in srcs):
+        subprocess.check_call(["g++", "-O1", "-std=c++17", "-fPIC", "-shared", "-o", _PLAN_SO, srcs[0]])
+    return _PLAN_SO
+
+
+def plan_lib():
+    global _plan_lib
+    if _plan_lib is None:
+        _plan_lib = C.CDLL(build_plan())
+    return _plan_lib
 
 
 def _p(a):

@@ -183,8 +183,8 @@ extern "C" int hs_solve_cost_batch(int batch, const double *Q45, const double *B
 
 extern "C" void hs_proj_affine_rc(double *E, int homog) { cvx::proj_affine<cvx::VAR_RC>(E, homog != 0); }
 
-// the first phase of the lane-hybrid schedule on the host: the general scalar core (impl 0: cvx::solve_problem<TWIN = false>, what
-// solve_lane_kernel<DBL> instantiates; dbl != 0: float64 eigen-solve) or the register-budgeted restatement (impl 1: cvxl::lane_phase,
+// the first phase of the lane-hybrid schedule on the host: the general scalar core (impl 0: cvx::solve_problem<TWIN = false>, the
+// reference statement -- no kernel instantiates it any more; dbl != 0: float64 eigen-solve) or the register-budgeted restatement (impl 1: cvxl::lane_phase,
 // what solve_lane2_kernel<false> instantiates; impl 2: cvxl::lane_phase_f64, its float64 instantiation).  status -1 = parked: handoff[b][0..54] = W, [55] = iteration count.
 extern "C" int hs_lane_phase(int batch, int n_p, const double *pts_2d, const double *pts_3d, int n_l, const double *line_2d, const double *line_3d,
                              const double *K, int K_per_problem, const cvx::Opts *opts, int iters, int impl, int dbl, double *R_out, double *t_out,
