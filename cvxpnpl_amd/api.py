@@ -155,7 +155,7 @@ def recover_multi_batch(res: "BatchResult", B, Q=None, n_threads: int = 0):
     """All poses of every rank > 1 problem of a batch result (solved with want_Z=True): the host-side cold path
     (cvxpnpl.py:507 -> :221-343) on all host cores.  B, Q: the outputs of assemble_batch for the same inputs.
     Returns (R [batch,4,3,3], t [batch,4,3], n_poses [batch]) as numpy arrays; n_poses is 0 for problems whose
-    status is not CVXPNPL_RANK_GT1."""
+    status is not CVXPNPL_RANK_GT1.  Slots beyond n_poses are NaN."""
     L = _lib.lib()
     if getattr(res, "Z", None) is None:
         raise ValueError("recover_multi_batch needs the SDP solutions: solve with want_Z=True")
@@ -180,7 +180,7 @@ def recover_multi_batch(res: "BatchResult", B, Q=None, n_threads: int = 0):
 def recover_multi_device(res: "BatchResult", B, Q=None):
     """recover_multi_batch on the DEVICE (cvxpnpl_recover_multi_device): every rank > 1 problem of a batch result solved
     with want_Z=True, one HIP launch, nothing leaves the GPU.  B, Q: outputs of assemble_batch (device tensors).  Returns
-    device tensors (R [batch,4,3,3], t [batch,4,3], n_poses [batch] int32)."""
+    device tensors (R [batch,4,3,3], t [batch,4,3], n_poses [batch] int32); slots beyond n_poses are NaN."""
     _require_gpu()
     L = _lib.lib()
     if getattr(res, "Z", None) is None:

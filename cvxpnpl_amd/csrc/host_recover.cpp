@@ -9,12 +9,19 @@
 
 extern "C" int cvxpnpl_recover_multi(const double *Z55, const double *B27, const double *Q45, double *R_out, double *t_out)
 {
-    return cvxr::recover_multi(Z55, B27, Q45, R_out, t_out);
+    // output contract (include/cvxpnpl_amd.h): slots k >= max(n_poses, 0) hold NaN
+    double R[36], t[12];
+    std::fill(R, R + 36, NAN);
+    std::fill(t, t + 12, NAN);
+    const int n = cvxr::recover_multi(Z55, B27, Q45, R, t);
+    std::copy(R, R + 36, R_out);
+    std::copy(t, t + 12, t_out);
+    return n;
 }
 
 // Batched form of the cold path: every problem of the batch whose status is CVXPNPL_RANK_GT1 (or every
 // problem when status == NULL) goes through cvxpnpl_recover_multi; the work is split over host threads
-// (n_threads <= 0: hardware concurrency).  n_poses[i] = 0 for problems that were skipped.
+// (n_threads <= 0: hardware concurrency).  n_poses[i] = 0 and NaN poses for problems that were skipped.
 extern "C" int cvxpnpl_recover_multi_batch(int64_t batch, const int32_t *status, const double *Z55, const double *B27, const double *Q45,
                                            double *R_out, double *t_out, int32_t *n_poses, int32_t n_threads)
 {
@@ -24,7 +31,12 @@ extern "C" int cvxpnpl_recover_multi_batch(int64_t batch, const int32_t *status,
     if ((int64_t)nt > batch) nt = batch > 0 ? (int)batch : 1;
     auto work = [&](int64_t lo, int64_t hi) {
         for (int64_t i = lo; i < hi; ++i) {
-            if (status && status[i] != CVXPNPL_RANK_GT1) { n_poses[i] = 0; continue; }
+            if (status && status[i] != CVXPNPL_RANK_GT1) {
+                n_poses[i] = 0;
+                std::fill(R_out + i * 36, R_out + (i + 1) * 36, NAN);
+                std::fill(t_out + i * 12, t_out + (i + 1) * 12, NAN);
+                continue;
+            }
             n_poses[i] = cvxpnpl_recover_multi(Z55 + i * 55, B27 + i * 27, Q45 ? Q45 + i * 45 : nullptr, R_out + i * 36, t_out + i * 12);
         }
     };

@@ -192,12 +192,15 @@ int cvxpnpl_solve_cost_batch(int64_t batch, const double *d_Q45, const double *d
  * A^T A from cvxpnpl_assemble_batch; when given, every recovered pose is Newton-polished on SO(3)
  * (the reference does not polish).  Returns the number of poses (2 or 4), 1 for a rank-1 Z, or -1
  * if rank is 0 / Z is not finite (reference: NotImplementedError / NaN sentinel).
+ * Output contract, the same for the three entry points: with n the return value (n_poses[i]), slots k < n of R_out / t_out
+ * hold the poses and every slot k >= max(n, 0) holds NaN -- also for a problem that failed (-1) or, in the batched forms,
+ * was skipped (0).  All 4 slots are always written; nothing of what the caller put there survives.
  */
 int cvxpnpl_recover_multi(const double *Z55, const double *B27, const double *Q45, double *R_out, double *t_out);
 
 /*
  * The same for a whole batch, on host threads (n_threads <= 0: all cores): problem i is recovered when
- * status == NULL or status[i] == CVXPNPL_RANK_GT1, skipped (n_poses[i] = 0) otherwise.  HOST pointers:
+ * status == NULL or status[i] == CVXPNPL_RANK_GT1, skipped (n_poses[i] = 0, NaN poses) otherwise.  HOST pointers:
  * Z55 [batch][55], B27 [batch][27], Q45 [batch][45] or NULL (copies of d_Z and of the outputs of
  * cvxpnpl_assemble_batch); R_out [batch][4][9], t_out [batch][4][3], n_poses [batch] (2, 4, 1, or -1 as above).
  * Returns 0, or -1 for bad arguments.  (the fast batched host path.)
@@ -210,7 +213,8 @@ int cvxpnpl_recover_multi_batch(int64_t batch, const int32_t *status, const doub
  * minimal RANSAC hypotheses flags 0.2 - 24 % of its problems, a planar batch all of them).  DEVICE pointers, same shapes
  * and meaning as cvxpnpl_recover_multi_batch: d_status [batch] or NULL, d_Z55 [batch][55] (cvxpnpl_solve_batch's d_Z),
  * d_B27 / d_Q45 (cvxpnpl_assemble_batch; d_Q45 may be NULL: no polish), d_R_out [batch][4][9], d_t_out [batch][4][3],
- * d_n_poses [batch] (0 = skipped, 2 / 4 / 1 / -1 as cvxpnpl_recover_multi).  Same source as the host path: bit-comparable.
+ * d_n_poses [batch] (0 = skipped, 2 / 4 / 1 / -1 as cvxpnpl_recover_multi; unused slots NaN as there).  Same source as the
+ * host path, two compilers: the pose sets agree to rounding.  batch == 0 launches nothing and returns 0.
  */
 int cvxpnpl_recover_multi_device(int64_t batch, const int32_t *d_status, const double *d_Z55, const double *d_B27, const double *d_Q45,
                                  double *d_R_out, double *d_t_out, int32_t *d_n_poses, void *stream);

@@ -28,6 +28,7 @@ def build(force=False):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-fopenmp", "-ffp-contract=off",
                                "-o", _SO, srcs[0]])
     build_plan()
+    build_recover()
     return _SO
 
 
@@ -61,6 +62,42 @@ def plan_lib():
     if _plan_lib is None:
         _plan_lib = C.CDLL(build_plan())
     return _plan_lib
+
+
+_RECOVER_SO = os.path.join(_HERE, "librecovershim.so")
+_recover_lib = None
+
+
+def build_recover():
+    """recover_shim.cpp: poly_roots and e6q3 of csrc/recover_core.h behind C entries"""
+    srcs = [os.path.join(_HERE, "recover_shim.cpp"), os.path.join(_CSRC, "recover_core.h"), os.path.join(_CSRC, "solver_core.h")]
+    if not os.path.exists(_RECOVER_SO) or os.path.getmtime(_RECOVER_SO) < max(os.path.getmtime(s) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _RECOVER_SO, srcs[0]])
+    return _RECOVER_SO
+
+
+def recover_lib():
+    global _recover_lib
+    if _recover_lib is None:
+        _recover_lib = C.CDLL(build_recover())
+    return _recover_lib
+
+
+def poly_roots(p):
+    """cvxr::poly_roots on descending coefficients -> complex roots"""
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    deg = len(p) - 1
+    re, im = np.zeros(8), np.zeros(8)
+    n = recover_lib().rs_poly_roots(_p(p), deg, _p(re), _p(im))
+    return re[:n] + 1j * im[:n]
+
+
+def e6q3(A):
+    """cvxr::e6q3 on rows [a^2 b^2 c^2 ab ac bc a b c 1] -> (a, b, c), one entry per solution"""
+    A = np.ascontiguousarray(A, dtype=np.float64).reshape(-1, 10)
+    a, b, c = np.zeros(4), np.zeros(4), np.zeros(4)
+    n = recover_lib().rs_e6q3(_p(A), len(A), _p(a), _p(b), _p(c))
+    return a[:max(n, 0)], b[:max(n, 0)], c[:max(n, 0)]
 
 
 def _p(a):
