@@ -197,6 +197,36 @@ def ransac_lib():
     return L
 
 
+# RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl.h): the fourth library
+RANSAC_PNPL_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_pnpl.so")
+RANSAC_PNPL_EXPORTS = ("cvxpnpl_ransac_pnpl_sample_assemble", "cvxpnpl_ransac_pnpl_score", "cvxpnpl_ransac_pnpl_select",
+                       "cvxpnpl_ransac_pnpl_assemble_consensus", "cvxpnpl_ransac_pnpl_refit_update", "cvxpnpl_ransac_pnpl_last_error")
+
+_ransac_pnpl_lib = None
+
+
+def ransac_pnpl_lib():
+    """Load libcvxpnpl_amd_ransac_pnpl.so (loudly)."""
+    global _ransac_pnpl_lib
+    if _ransac_pnpl_lib is not None:
+        return _ransac_pnpl_lib
+    if not os.path.exists(RANSAC_PNPL_LIB_PATH):
+        raise LibraryMissing(f"{RANSAC_PNPL_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(RANSAC_PNPL_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    scenes = [p, i64, p, i64]  # d_pt_offsets, n_pts, d_ln_offsets, n_lines
+    L.cvxpnpl_ransac_pnpl_sample_assemble.argtypes = [i64, i32] + scenes + [p, p, p, p, p, p, i32, p, p, p, p]
+    L.cvxpnpl_ransac_pnpl_score.argtypes = [i64, i32] + scenes + [p, p, p, C.c_uint32, p, i32, p, p, p, p, C.c_double, p, p]
+    L.cvxpnpl_ransac_pnpl_select.argtypes = [i64, i32] + scenes + [p, p, p, p, p, i32, p, p, p, p, C.c_double, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_pnpl_assemble_consensus.argtypes = [i64] + scenes + [p, p, p, p, p, p, p, i32, p, p, p, p]
+    L.cvxpnpl_ransac_pnpl_refit_update.argtypes = [i64] + scenes + [p, p, p, p, p, i32, p, p, p, p, C.c_double, p, p, p, p, p, p]
+    for name in RANSAC_PNPL_EXPORTS[:-1]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_ransac_pnpl_last_error.restype = C.c_char_p
+    _ransac_pnpl_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -53,13 +53,26 @@ def grad_compile_cmd(out=GRAD_OUT):
 RANSAC_SRC = os.path.join(HERE, "csrc", "ransac_hip.hip")
 RANSAC_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac.so")
 RANSAC_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac.resources.txt")
-RANSAC_DEPS = [RANSAC_SRC, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+RANSAC_DEPS = [RANSAC_SRC, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac.h")]
 
 
 def ransac_compile_cmd(out=RANSAC_OUT):
     return [hipcc(), "-Rpass-analysis=kernel-resource-usage", "--offload-arch=gfx950", "-O3", "-std=c++17", "-shared", "-fPIC", "-Wno-unused-value",
             "-o", out, RANSAC_SRC]
+
+
+# RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl.h): the fourth library, same flags as the third
+RANSAC_PNPL_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_hip.hip")
+RANSAC_PNPL_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.so")
+RANSAC_PNPL_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.resources.txt")
+RANSAC_PNPL_DEPS = [RANSAC_PNPL_SRC, os.path.join(HERE, "csrc", "ransac_pnpl_kernel.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                    os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                    os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_pnpl.h")]
+
+
+def ransac_pnpl_compile_cmd(out=RANSAC_PNPL_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_PNPL_SRC]
 
 
 def _build_one(out, resources, deps, cmd, force, verbose):
@@ -88,11 +101,16 @@ def build_ransac(force=False, verbose=False):
     return _build_one(RANSAC_OUT, RANSAC_RESOURCES, RANSAC_DEPS, ransac_compile_cmd(), force, verbose)
 
 
+def build_ransac_pnpl(force=False, verbose=False):
+    return _build_one(RANSAC_PNPL_OUT, RANSAC_PNPL_RESOURCES, RANSAC_PNPL_DEPS, ransac_pnpl_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All three libraries; returns the solver's (OUT)."""
+    """All four libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
+    build_ransac_pnpl(force, verbose)
     return OUT
 
 

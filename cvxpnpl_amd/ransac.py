@@ -339,3 +339,354 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     h = head.cpu()   # the call's one synchronisation
     return {"R": R, "t": t, "inliers": mask.view(torch.bool), "offsets": sc.offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3],
             "best_index": h[:, 2], "head": h, "sizes": sc.sizes, "n_hyp": int(n_hyp)}
+
+
+# ---- points AND lines, many scenes (include/cvxpnpl_amd_ransac_pnpl.h) --------------------------------------------
+# The robust layer of pnpl: a scene is P_f point and L_f line correspondences, a minimal set is four correspondences of their union.  Its
+# shape (4+0 .. 0+4) differs from hypothesis to hypothesis, and cvxpnpl_solve_batch takes one (n_p, n_l) per batch, so the sampling kernel
+# assembles every hypothesis' cost itself and the F * n_hyp minimal solves go through the cost seam, as the refits do.  The kernels are
+# those of libcvxpnpl_amd_ransac_pnpl.so; an inlier count is points plus lines, a line counting once.
+
+
+class PnplScenes:
+    """F scenes of points and lines packed on one device: x [sum P,2], X [sum P,3], l2 [sum L,2,2], l3 [sum L,2,3] float64; offsets and
+    line_offsets [F+1] int64 (device); sizes, line_sizes (host tuples); K [3,3] or [F,3,3]; seeds int64 [F] on the device, or None.
+    Built by pack_pnpl_scenes."""
+
+    def __init__(self, x, X, l2, l3, offsets, line_offsets, sizes, line_sizes, K, seeds=None):
+        self.x, self.X, self.l2, self.l3, self.offsets, self.line_offsets, self.K, self.seeds = x, X, l2, l3, offsets, line_offsets, K, seeds
+        self.sizes, self.line_sizes = tuple(sizes), tuple(line_sizes)
+        self.F, self.total, self.line_total = len(self.sizes), int(sum(self.sizes)), int(sum(self.line_sizes))
+        self.per_scene_K, self.device = int(K.dim() == 3), K.device
+
+
+def _numel(a):
+    n = 1
+    for s in _shape(a):
+        n *= int(s)
+    return n
+
+
+def _pair_sizes(a2, a3, sizes, what, tail2, tail3):
+    """Sizes of one kind of correspondence (points or lines) over the scenes, or None when the pair is absent.  tail2 / tail3: the shape
+    of one 2D / 3D record.  A scene's entry may be None or empty."""
+    if a2 is None and a3 is None:
+        if sizes is not None and any(int(s) for s in sizes):
+            raise ValueError(f"sizes of {what} given without {what}")
+        return None
+    if a2 is None or a3 is None:
+        raise ValueError(f"{what}: the 2D and the 3D half go together")
+    if sizes is None:
+        if not isinstance(a2, (list, tuple)) or not isinstance(a3, (list, tuple)):
+            raise ValueError(f"{what}: scenes are a list of F 2D arrays and a list of F 3D arrays, or packed arrays with their sizes")
+        if len(a2) != len(a3):
+            raise ValueError(f"{len(a2)} scenes of 2D {what} for {len(a3)} scenes of 3D {what}")
+        out = []
+        for f, (a, b) in enumerate(zip(a2, a3)):
+            na = 0 if a is None or _numel(a) == 0 else None
+            nb = 0 if b is None or _numel(b) == 0 else None
+            if na is None:
+                sa = _shape(a)
+                if len(sa) != 1 + len(tail2) or sa[1:] != tail2:
+                    raise ValueError(f"scene {f}: expected 2D {what} [n,{','.join(map(str, tail2))}], got {sa}")
+                na = int(sa[0])
+            if nb is None:
+                sb = _shape(b)
+                if len(sb) != 1 + len(tail3) or sb[1:] != tail3:
+                    raise ValueError(f"scene {f}: expected 3D {what} [n,{','.join(map(str, tail3))}], got {sb}")
+                nb = int(sb[0])
+            if na != nb:
+                raise ValueError(f"scene {f}: {na} 2D {what} for {nb} 3D {what}")
+            out.append(na)
+        return out
+    out = [int(s) for s in sizes]
+    if any(s < 0 for s in out):
+        raise ValueError(f"negative size among the sizes of {what}")
+    sa, sb = _shape(a2), _shape(a3)
+    na = 0 if _numel(a2) == 0 else None
+    nb = 0 if _numel(a3) == 0 else None
+    if na is None:
+        if len(sa) != 1 + len(tail2) or sa[1:] != tail2:
+            raise ValueError(f"packed scenes: expected 2D {what} [n,{','.join(map(str, tail2))}], got {sa}")
+        na = int(sa[0])
+    if nb is None:
+        if len(sb) != 1 + len(tail3) or sb[1:] != tail3:
+            raise ValueError(f"packed scenes: expected 3D {what} [n,{','.join(map(str, tail3))}], got {sb}")
+        nb = int(sb[0])
+    if na != nb:
+        raise ValueError(f"packed scenes: {na} 2D {what} for {nb} 3D {what}")
+    if sum(out) != na:
+        raise ValueError(f"sizes add up to {sum(out)}, the packed scenes hold {na} {what}")
+    return out
+
+
+def _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes):
+    """Host-side validation of a scene set of points and lines (nothing here needs a GPU): returns (sizes, line_sizes).  ValueError for an
+    empty set, a scene of fewer than four correspondences in total, 2D / 3D lengths that differ (points or lines), different numbers of
+    point scenes and line scenes, sizes that do not add up, or a K that is neither [3,3] nor [F,3,3]."""
+    ps = _pair_sizes(pts_2d, pts_3d, sizes, "points", (2,), (3,))
+    ls = _pair_sizes(line_2d, line_3d, line_sizes, "lines", (2, 2), (2, 3))
+    if ps is None and ls is None:
+        raise ValueError("no scenes: neither points nor lines")
+    if ps is not None and ls is not None and len(ps) != len(ls):
+        raise ValueError(f"{len(ps)} scenes of points for {len(ls)} scenes of lines")
+    F = len(ps if ps is not None else ls)
+    ps = [0] * F if ps is None else ps
+    ls = [0] * F if ls is None else ls
+    if F == 0:
+        raise ValueError("no scenes")
+    for f in range(F):
+        if ps[f] + ls[f] < 4:
+            raise ValueError(f"scene {f} has {ps[f]} points and {ls[f]} lines: a minimal set needs 4 correspondences")
+    sk = _shape(K)
+    if sk != (3, 3) and sk != (F, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{F},3,3], got {sk}")
+    return ps, ls
+
+
+def _pack_half(a, tail, device):
+    """One packed correspondence array [n, *tail] on the device from a list of per-scene arrays (None / empty entries dropped), a packed
+    array, or None."""
+    if isinstance(a, (list, tuple)):
+        a = [b for b in a if b is not None and _numel(b) > 0]
+        if a and any(isinstance(b, torch.Tensor) for b in a):
+            return torch.cat([torch.as_tensor(b, dtype=torch.float64, device=device).reshape((-1,) + tail) for b in a]).contiguous()
+        a = _np.concatenate([_np.asarray(b, dtype=_np.float64).reshape((-1,) + tail) for b in a]) if a else None
+    if a is None or _numel(a) == 0:
+        return torch.zeros((0,) + tail, dtype=torch.float64, device=device)
+    if not isinstance(a, torch.Tensor):
+        a = torch.as_tensor(_np.ascontiguousarray(a, dtype=_np.float64))
+    return a.to(device=device, dtype=torch.float64).reshape((-1,) + tail).contiguous()
+
+
+def _seed_words(seeds):
+    return _np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=_np.uint64).view(_np.int64)
+
+
+def pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=None, line_sizes=None, device=None, seeds=None) -> PnplScenes:
+    """Validate (on the host) and pack a scene set of points and lines on the device; the argument order is pnpl's.  pts_2d / pts_3d: lists
+    of F arrays [P_f,2] / [P_f,3], or packed with `sizes`; line_2d / line_3d: lists of F arrays [L_f,2,2] / [L_f,2,3], or packed with
+    `line_sizes`.  Either pair may be None or empty, for all scenes or for single ones.  K [3,3] or [F,3,3].  seeds (optional, F ints):
+    both offset arrays and the seeds travel in ONE host-to-device copy."""
+    ps, ls = _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes)
+    F = len(ps)
+    if seeds is not None and len(seeds) != F:
+        raise ValueError(f"{len(seeds)} seeds for {F} scenes")
+    _require_gpu()
+    device = _pick_device(device, pts_3d, line_3d, pts_2d, line_2d, K)
+    meta = _np.zeros(2 * (F + 1) + (F if seeds is not None else 0), dtype=_np.int64)  # both offset arrays, then the seeds: one copy
+    _np.cumsum(ps, out=meta[1:F + 1])
+    _np.cumsum(ls, out=meta[F + 2:2 * F + 2])
+    if seeds is not None:
+        meta[2 * F + 2:] = _seed_words(seeds)
+    meta = torch.as_tensor(meta).to(device)
+    sd = meta[2 * F + 2:] if seeds is not None else None
+    Kd = K if isinstance(K, torch.Tensor) else torch.as_tensor(_np.ascontiguousarray(K, dtype=_np.float64))
+    return PnplScenes(_pack_half(pts_2d, (2,), device), _pack_half(pts_3d, (3,), device), _pack_half(line_2d, (2, 2), device),
+                      _pack_half(line_3d, (2, 3), device), meta[:F + 1], meta[F + 1:2 * F + 2], ps, ls, _to_dev(Kd, device), sd)
+
+
+def _chk_pnpl_scenes(sc: PnplScenes):
+    dev = sc.device
+    if dev.type != "cuda":
+        raise ValueError(f"the scenes are on {dev}: cvxpnpl_amd has no CPU path")
+    _chk(sc.x, "scene pts_2d", torch.float64, (sc.total, 2), dev)
+    _chk(sc.X, "scene pts_3d", torch.float64, (sc.total, 3), dev)
+    _chk(sc.l2, "scene line_2d", torch.float64, (sc.line_total, 2, 2), dev)
+    _chk(sc.l3, "scene line_3d", torch.float64, (sc.line_total, 2, 3), dev)
+    _chk(sc.offsets, "offsets", torch.int64, (sc.F + 1,), dev)
+    _chk(sc.line_offsets, "line_offsets", torch.int64, (sc.F + 1,), dev)
+    _chk(sc.K, "K", torch.float64, (sc.F, 3, 3) if sc.per_scene_K else (3, 3), dev)
+
+
+def _scene_args(sc: PnplScenes):
+    return _ptr(sc.offsets), sc.total, _ptr(sc.line_offsets), sc.line_total
+
+
+def _data_args(sc: PnplScenes):
+    return _ptr(sc.x), _ptr(sc.X), _ptr(sc.l2), _ptr(sc.l3)
+
+
+def _call_pnpl(sc: PnplScenes, name, *args):
+    with torch.cuda.device(sc.device):
+        L = _lib.ransac_pnpl_lib()
+        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_pnpl_last_error().decode()}")
+
+
+def sample_assemble_scenes(sc: PnplScenes, n_hyp: int, seeds=None, want_idx: bool = False):
+    """cvxpnpl_ransac_pnpl_sample_assemble: n_hyp minimal sets per scene, drawn over the union of the scene's points and lines (index c <
+    P_f: point c; otherwise line c - P_f; scene f draws what synth.philox_minimal_sets(n_hyp, P_f + L_f, 4, seeds[f]) draws) and
+    assembled in place.  Returns (Q45 [F*n_hyp,45], B27 [F*n_hyp,27]), the inputs of solve_cost_batch, and with want_idx idx [F*n_hyp,4]
+    int32.  seeds: a sequence of F ints (None: the seeds packed with the scenes)."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    H, dev = int(n_hyp), sc.device
+    if H < 0:
+        raise ValueError("n_hyp must not be negative")
+    if seeds is None:
+        if sc.seeds is None:
+            raise ValueError("no seeds: give them here or to pack_pnpl_scenes")
+        sd = sc.seeds
+    else:
+        if len(seeds) != sc.F:
+            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
+        sd = torch.as_tensor(_seed_words(seeds)).to(dev)
+    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
+    n = sc.F * H
+    Qt = torch.empty((n, 45), dtype=torch.float64, device=dev)
+    Bt = torch.empty((n, 27), dtype=torch.float64, device=dev)
+    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
+    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_sample_assemble", sc.F, H, *_scene_args(sc), _ptr(sd), *_data_args(sc), _ptr(sc.K), sc.per_scene_K, _ptr(idx),
+               _ptr(Qt), _ptr(Bt))
+    return (Qt, Bt, idx) if want_idx else (Qt, Bt)
+
+
+def score_pnpl_scenes(sc: PnplScenes, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
+    """cvxpnpl_ransac_pnpl_score: count [F*H] int32, the point plus line inliers of hypothesis (f, h) = (R, t)[f*H + h] in scene f."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F:
+        raise ValueError("R must be [F*H,3,3]")
+    n = R.shape[0]
+    _chk(R, "R", torch.float64, (n, 3, 3), sc.device)
+    _chk(t, "t", torch.float64, (n, 3), sc.device)
+    if status is not None:
+        _chk(status, "status", torch.int32, (n,), sc.device)
+    count = torch.empty((n,), dtype=torch.int32, device=sc.device)
+    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_score", sc.F, n // sc.F, *_scene_args(sc), _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable), _ptr(sc.K),
+               sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(count))
+    return count
+
+
+def select_pnpl_scenes(sc: PnplScenes, count, R, t, status, thresh: float = 2.0):
+    """cvxpnpl_ransac_pnpl_select: per scene the hypothesis of the highest count (lowest index on a tie).  Returns R [F,3,3], t [F,3],
+    head [F,4] int32 = (status, inliers, index within the scene, certified hypotheses), mask_pts [sum P] and mask_lines [sum L] uint8.
+    No synchronisation."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F or R.shape[0] < sc.F:
+        raise ValueError("R must be [F*H,3,3] with H >= 1")
+    n, dev = R.shape[0], sc.device
+    _chk(R, "R", torch.float64, (n, 3, 3), dev)
+    _chk(t, "t", torch.float64, (n, 3), dev)
+    _chk(status, "status", torch.int32, (n,), dev)
+    _chk(count, "count", torch.int32, (n,), dev)
+    oR = torch.empty((sc.F, 3, 3), dtype=torch.float64, device=dev)
+    ot = torch.empty((sc.F, 3), dtype=torch.float64, device=dev)
+    head = torch.empty((sc.F, 4), dtype=torch.int32, device=dev)
+    mp = torch.empty((sc.total,), dtype=torch.uint8, device=dev)
+    ml = torch.empty((sc.line_total,), dtype=torch.uint8, device=dev)
+    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_select", sc.F, n // sc.F, *_scene_args(sc), _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
+               sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(oR), _ptr(ot), _ptr(head), _ptr(mp), _ptr(ml))
+    return oR, ot, head, mp, ml
+
+
+def assemble_pnpl_consensus(sc: PnplScenes, mask_pts, mask_lines):
+    """cvxpnpl_ransac_pnpl_assemble_consensus: (B27 [F,27], Q45 [F,45], count [F] int32) of every scene's masked points and lines (uint8
+    masks [sum P] / [sum L], non-zero = taken); feed solve_cost_batch.  Fewer than three correspondences taken: NaN for that scene."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    dev = sc.device
+    _chk(mask_pts, "mask_pts", torch.uint8, (sc.total,), dev)
+    _chk(mask_lines, "mask_lines", torch.uint8, (sc.line_total,), dev)
+    Bt = torch.empty((sc.F, 27), dtype=torch.float64, device=dev)
+    Qt = torch.empty((sc.F, 45), dtype=torch.float64, device=dev)
+    cnt = torch.empty((sc.F,), dtype=torch.int32, device=dev)
+    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_assemble_consensus", sc.F, *_scene_args(sc), *_data_args(sc), _ptr(mask_pts), _ptr(mask_lines), _ptr(sc.K),
+               sc.per_scene_K, _ptr(Bt), _ptr(Qt), _ptr(cnt))
+    return Bt, Qt, cnt
+
+
+def refit_update_pnpl_scenes(sc: PnplScenes, fit, fit_count, thresh, R, t, head, mask_pts, mask_lines):
+    """cvxpnpl_ransac_pnpl_refit_update: per scene, take the refitted pose fit.R[f] / fit.t[f] -- pose, status, both masks and count
+    together, in place -- when it is usable and keeps at least head[f,1] inliers.  One launch, no synchronisation."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    dev = sc.device
+    _chk(fit.R, "fit.R", torch.float64, (sc.F, 3, 3), dev)
+    _chk(fit.t, "fit.t", torch.float64, (sc.F, 3), dev)
+    _chk(fit.status, "fit.status", torch.int32, (sc.F,), dev)
+    _chk(fit_count, "fit_count", torch.int32, (sc.F,), dev)
+    _chk(R, "R", torch.float64, (sc.F, 3, 3), dev)
+    _chk(t, "t", torch.float64, (sc.F, 3), dev)
+    _chk(head, "head", torch.int32, (sc.F, 4), dev)
+    _chk(mask_pts, "mask_pts", torch.uint8, (sc.total,), dev)
+    _chk(mask_lines, "mask_lines", torch.uint8, (sc.line_total,), dev)
+    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_refit_update", sc.F, *_scene_args(sc), _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count), _ptr(sc.K),
+               sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask_pts), _ptr(mask_lines))
+
+
+# The cost seam does not tell the solver how many correspondences stand behind a cost, and its launch plan then assumes a well
+# over-determined problem: the interior-point path for slowly converging problems starts after 128 iterations, beyond the 100 a
+# hypothesis is given.  Minimal problems are the slow ones (DESIGN.md section 4: a fifth is still open after 32 iterations), and
+# cvxpnpl_solve_batch hands four-correspondence problems over after 32; the minimal solves here ask for the same.
+MINIMAL_SOLVER_OPTS = {"rescue_from": 32}
+
+
+def solve_minimal_costs(Q45, B27, eps: float = 1e-6, max_iters: int = 100, device=None, **solver_opts):
+    """solve_cost_batch on the costs of minimal sets (sample_assemble_scenes), with MINIMAL_SOLVER_OPTS unless the caller overrides them."""
+    return solve_cost_batch(Q45, B27, eps=eps, max_iters=max_iters, device=device, **{**MINIMAL_SOLVER_OPTS, **solver_opts})
+
+
+def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0,
+                      refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, **solver_opts):
+    """Robust PnPL for F scenes of different sizes in one launch sequence; the argument order is pnpl's.
+
+    Scenes: lists of F arrays pts_2d[f] [P_f,2] / pts_3d[f] [P_f,3] / line_2d[f] [L_f,2,2] / line_3d[f] [L_f,2,3], or packed arrays with
+    `sizes` / `line_sizes` (host sequences of F ints).  Either pair may be None or empty, for all scenes or for single ones; a scene needs
+    P_f + L_f >= 4.  K [3,3] or [F,3,3].  n_hyp minimal sets of four correspondences are drawn PER SCENE from the union of its points and
+    lines; seed is an int (scene f uses seed + f) or a sequence of F ints.  A point is an inlier when it reprojects within thresh pixels in
+    front of the camera, a line when both projected end points lie within thresh pixels of its image line, in front of the camera.
+    Returns a dict: R [F,3,3], t [F,3], inliers_pts (packed bool [sum P]) with offsets [F+1], inliers_lines (packed bool [sum L]) with
+    line_offsets [F+1] on the device; n_inliers (points + lines, a line counting once), status, n_certified, best_index [F] (host, columns
+    of the one read-back `head` [F,4]); sizes, line_sizes, n_hyp.  One host synchronisation per call."""
+    ps, ls = _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes)
+    F = len(ps)
+    if seed is None:
+        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
+    if isinstance(seed, (int, _np.integer)):
+        seeds = [int(seed) + f for f in range(F)]
+    else:
+        seeds = [int(s) for s in seed]
+        if len(seeds) != F:
+            raise ValueError(f"{len(seeds)} seeds for {F} scenes")
+    if int(n_hyp) < 1:
+        raise ValueError("n_hyp must be at least 1")
+    sc = pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=sizes, line_sizes=line_sizes, device=device, seeds=seeds)
+    # no torch kernel from here to the read-back: draw + minimal assembly, the F * n_hyp minimal solves at the cost seam ...
+    Qh, Bh = sample_assemble_scenes(sc, n_hyp)
+    res = solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+    count = score_pnpl_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+    R, t, head, mp, ml = select_pnpl_scenes(sc, count, res.R, res.t, res.status, thresh)
+    if refit:
+        for _ in range(max(1, int(refit_rounds))):  # ... and the F refits of the consensus sets in one more solve there
+            Bt, Qt, cnt = assemble_pnpl_consensus(sc, mp, ml)
+            fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
+            refit_update_pnpl_scenes(sc, fit, cnt, thresh, R, t, head, mp, ml)
+    h = head.cpu()   # the call's one synchronisation
+    return {"R": R, "t": t, "inliers_pts": mp.view(torch.bool), "offsets": sc.offsets, "inliers_lines": ml.view(torch.bool),
+            "line_offsets": sc.line_offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3], "best_index": h[:, 2], "head": h,
+            "sizes": sc.sizes, "line_sizes": sc.line_sizes, "n_hyp": int(n_hyp)}
+
+
+def ransac_pnl_batch(line_2d, line_3d, K, **kw):
+    """Robust PnL for F scenes of lines: ransac_pnpl_batch without points (packed lines: `line_sizes`)."""
+    return ransac_pnpl_batch(None, line_2d, None, line_3d, K, **kw)
+
+
+def ransac_pnpl(pts_2d, line_2d, pts_3d, line_3d, K, **kw):
+    """Robust PnPL for ONE scene: pts_2d [P,2], line_2d [L,2,2], pts_3d [P,3], line_3d [L,2,3] (either pair may be None), K [3,3].  The
+    batch call with F = 1 (scene 0 uses `seed` itself), unpacked: R [3,3], t [3], inliers_pts [P], inliers_lines [L] on the device;
+    n_inliers, status, n_certified, best_index (ints), n_hyp."""
+    out = ransac_pnpl_batch(None if pts_2d is None else [pts_2d], None if line_2d is None else [line_2d], None if pts_3d is None else [pts_3d],
+                            None if line_3d is None else [line_3d], K, **kw)
+    h = out["head"][0]
+    return {"R": out["R"][0], "t": out["t"][0], "inliers_pts": out["inliers_pts"], "inliers_lines": out["inliers_lines"], "n_inliers": int(h[1]),
+            "status": int(h[0]), "n_certified": int(h[3]), "best_index": int(h[2]), "n_hyp": out["n_hyp"]}
+
+
+def ransac_pnl(line_2d, line_3d, K, **kw):
+    """Robust PnL for ONE scene: ransac_pnpl without points."""
+    return ransac_pnpl(None, line_2d, None, line_3d, K, **kw)

@@ -85,6 +85,32 @@ def make_ransac(n_hyp, n_corr=100, outlier_frac=0.3, sigma=0.0, seed=46, K=K_KIN
             "scene_2d": x, "scene_3d": P[0], "inlier": inlier, "R_gt": R[0], "t_gt": t[0], "K": np.array(K, dtype=np.float64)}
 
 
+def make_ransac_pnpl(n_pts=100, n_lines=50, outlier_frac=0.3, sigma=0.0, seed=46, K=K_KINECT, width=640, height=480, line_outlier_frac=None):
+    """One scene of n_pts point and n_lines line correspondences with outliers, for RANSAC over both: one pose, points and line end
+    points from the 0.6 cube, projected, N(0, sigma^2) noise on all 2D samples; a fraction of the points and, separately, of the lines
+    (line_outlier_frac, default outlier_frac) has its 2D samples replaced by uniform image clutter.  Returns pts_2d [n_pts,2], pts_3d
+    [n_pts,3], line_2d [n_lines,2,2], line_3d [n_lines,2,3], the ground-truth flags inlier_pts / inlier_lines, R_gt, t_gt, K."""
+    rs = np.random.RandomState(seed)
+    R, t = random_poses(rs, 1)
+    P = LENGTH * (rs.random_sample((1, n_pts + 2 * n_lines, 3)) - 0.5)
+    x = project(P, K, R, t)[0]
+    if sigma > 0:
+        x = x + rs.normal(scale=sigma, size=x.shape)
+    x2, l2 = np.ascontiguousarray(x[:n_pts]), np.ascontiguousarray(x[n_pts:].reshape(n_lines, 2, 2))
+    size = np.array([width, height])
+    n_out = int(round(outlier_frac * n_pts))
+    out_p = rs.choice(n_pts, n_out, replace=False) if n_out else np.zeros(0, int)
+    x2[out_p] = rs.random_sample((n_out, 2)) * size
+    n_out_l = int(round((outlier_frac if line_outlier_frac is None else line_outlier_frac) * n_lines))
+    out_l = rs.choice(n_lines, n_out_l, replace=False) if n_out_l else np.zeros(0, int)
+    l2[out_l] = rs.random_sample((n_out_l, 2, 2)) * size
+    inl_p, inl_l = np.ones(n_pts, bool), np.ones(n_lines, bool)
+    inl_p[out_p] = False
+    inl_l[out_l] = False
+    return {"pts_2d": x2, "pts_3d": np.ascontiguousarray(P[0, :n_pts]), "line_2d": l2, "line_3d": np.ascontiguousarray(P[0, n_pts:].reshape(n_lines, 2, 3)),
+            "inlier_pts": inl_p, "inlier_lines": inl_l, "R_gt": R[0], "t_gt": t[0], "K": np.array(K, dtype=np.float64)}
+
+
 def geodesic(Ra, Rb):
     """Batched rotation angle of Ra^T Rb, accurate at tiny angles."""
     D = np.swapaxes(Ra, -1, -2) @ Rb
