@@ -227,6 +227,42 @@ def ransac_pnpl_lib():
     return L
 
 
+# reprojection refinement of poses (include/cvxpnpl_amd_refine.h): the fifth library
+REFINE_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_refine.so")
+REFINE_EXPORTS = ("cvxpnpl_refine_batch", "cvxpnpl_refine_scenes", "cvxpnpl_refine_batch_host", "cvxpnpl_refine_last_error", "cvxpnpl_refine_version")
+REFINE_CONVERGED, REFINE_MAXITER, REFINE_SKIPPED, REFINE_SINGULAR, REFINE_BEHIND = 0, 1, 2, 3, 4  # CVXPNPL_REFINE_*
+
+
+class RefineOpts(C.Structure):
+    """cvxpnpl_refine_opts_t"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("step_tol", C.c_double), ("lambda0", C.c_double), ("sigma_px", C.c_double)]
+
+
+_refine_lib = None
+
+
+def refine_lib():
+    """Load libcvxpnpl_amd_refine.so (loudly)."""
+    global _refine_lib
+    if _refine_lib is not None:
+        return _refine_lib
+    if not os.path.exists(REFINE_LIB_PATH):
+        raise LibraryMissing(f"{REFINE_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(REFINE_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    pose = [p, i32, p, p, p, i64, C.c_uint32, p, p, C.POINTER(RefineOpts)]  # K, K_per, R, t, status, stride, admit, masks, opts
+    outs = [p, p, p, p, p, p, p]                                            # R, t, cost, iters, status, n_live, cov
+    L.cvxpnpl_refine_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [p]
+    L.cvxpnpl_refine_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [i32]
+    L.cvxpnpl_refine_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + outs + [p]
+    for name in REFINE_EXPORTS[:3]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_refine_last_error.restype = C.c_char_p
+    L.cvxpnpl_refine_version.restype = C.c_char_p
+    _refine_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -75,6 +75,20 @@ def ransac_pnpl_compile_cmd(out=RANSAC_PNPL_OUT):
     return ransac_compile_cmd(out)[:-1] + [RANSAC_PNPL_SRC]
 
 
+# reprojection refinement of poses (include/cvxpnpl_amd_refine.h): the fifth library, device and host entry points as in the second
+REFINE_SRC = os.path.join(HERE, "csrc", "refine_hip.hip")
+REFINE_HOST_SRC = os.path.join(HERE, "csrc", "host_refine.cpp")
+REFINE_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine.so")
+REFINE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine.resources.txt")
+REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"),
+               os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+               os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine.h")]
+
+
+def refine_compile_cmd(out=REFINE_OUT):
+    return grad_compile_cmd(out)[:-2] + [REFINE_SRC, REFINE_HOST_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -105,12 +119,17 @@ def build_ransac_pnpl(force=False, verbose=False):
     return _build_one(RANSAC_PNPL_OUT, RANSAC_PNPL_RESOURCES, RANSAC_PNPL_DEPS, ransac_pnpl_compile_cmd(), force, verbose)
 
 
+def build_refine(force=False, verbose=False):
+    return _build_one(REFINE_OUT, REFINE_RESOURCES, REFINE_DEPS, refine_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All four libraries; returns the solver's (OUT)."""
+    """All five libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
     build_ransac_pnpl(force, verbose)
+    build_refine(force, verbose)
     return OUT
 
 

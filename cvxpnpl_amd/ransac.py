@@ -303,8 +303,32 @@ def refit_update_scenes(sc: Scenes, fit, fit_count, thresh, R, t, head, mask):
           sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask))
 
 
+class _Fit:
+    """What refit_update_*_scenes reads of a refit: R, t, status."""
+
+    def __init__(self, R, t, status):
+        self.R, self.t, self.status = R, t, status
+
+
+def _polish(sc, R, t, head, mask_pts, mask_lines, thresh):
+    """The last step of the two batch calls with polish=True: one refine_scenes launch over the consensus masks, then
+    the scenes' refit_update kernel, which takes the polished pose -- with its masks and count -- only when it keeps at least the consensus
+    it was fitted to.  Its candidate status is the scene's own solve status when the refinement ended CONVERGED or MAXITER, and 3 (never
+    taken) otherwise.  No synchronisation.  Returns the "refine" entry of the result."""
+    from .refine import refine_scenes
+
+    res = refine_scenes(sc, R, t, mask_pts=mask_pts, mask_lines=mask_lines, status=head[:, 0])
+    fit = _Fit(res.R, res.t, torch.where(res.status <= 1, head[:, 0], torch.full_like(res.status, 3)))
+    cnt = head[:, 1].contiguous()
+    if mask_lines is None:
+        refit_update_scenes(sc, fit, cnt, thresh, R, t, head, mask_pts)
+    else:
+        refit_update_pnpl_scenes(sc, fit, cnt, thresh, R, t, head, mask_pts, mask_lines)
+    return {"cost": res.cost, "iters": res.iters, "status": res.status}
+
+
 def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
-                     refit_rounds: int = 1, sizes=None, device=None, **solver_opts):
+                     refit_rounds: int = 1, sizes=None, device=None, polish: bool = False, **solver_opts):
     """Robust PnP for F scenes of different sizes in one launch sequence (what ransac_pnp does for one scene per call).
 
     Scenes: lists of F arrays pts_2d[f] [M_f,2] / pts_3d[f] [M_f,3], or packed [sum M,2] / [sum M,3] with `sizes` (a host sequence of F
@@ -312,7 +336,9 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     scene f draws exactly the minimal sets ransac_pnp(scene f, seed=seed_f, n_hyp=n_hyp) draws.
     Returns a dict: R [F,3,3], t [F,3], inliers (packed bool [sum M]) and offsets [F+1] (scene f's inliers are
     inliers[offsets[f]:offsets[f+1]]) on the device; n_inliers, status, n_certified, best_index [F] (host, columns of the one read-back
-    `head` [F,4], each row what select_best's head is for one scene); sizes, n_hyp.  One host synchronisation per call."""
+    `head` [F,4], each row what select_best's head is for one scene); sizes, n_hyp.  One host synchronisation per call.
+    polish=True: after the refits the pose is refined on the pixel reprojection error of its consensus set (refine.refine_scenes) and kept
+    when it holds at least that consensus; the result gains "refine": device tensors cost [F,2], iters, status [F]."""
     szs = _check_scenes(pts_2d, pts_3d, K, sizes)
     F = len(szs)
     if seed is None:
@@ -336,9 +362,13 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
             Bt, Qt, cnt = assemble_consensus(sc, mask)
             fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
             refit_update_scenes(sc, fit, cnt, thresh, R, t, head, mask)
+    refined = _polish(sc, R, t, head, mask, None, thresh) if polish else None
     h = head.cpu()   # the call's one synchronisation
-    return {"R": R, "t": t, "inliers": mask.view(torch.bool), "offsets": sc.offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3],
-            "best_index": h[:, 2], "head": h, "sizes": sc.sizes, "n_hyp": int(n_hyp)}
+    out = {"R": R, "t": t, "inliers": mask.view(torch.bool), "offsets": sc.offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3],
+           "best_index": h[:, 2], "head": h, "sizes": sc.sizes, "n_hyp": int(n_hyp)}
+    if polish:
+        out["refine"] = refined
+    return out
 
 
 # ---- points AND lines, many scenes (include/cvxpnpl_amd_ransac_pnpl.h) --------------------------------------------
@@ -631,7 +661,7 @@ def solve_minimal_costs(Q45, B27, eps: float = 1e-6, max_iters: int = 100, devic
 
 
 def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0,
-                      refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, **solver_opts):
+                      refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, polish: bool = False, **solver_opts):
     """Robust PnPL for F scenes of different sizes in one launch sequence; the argument order is pnpl's.
 
     Scenes: lists of F arrays pts_2d[f] [P_f,2] / pts_3d[f] [P_f,3] / line_2d[f] [L_f,2,2] / line_3d[f] [L_f,2,3], or packed arrays with
@@ -641,7 +671,8 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
     front of the camera, a line when both projected end points lie within thresh pixels of its image line, in front of the camera.
     Returns a dict: R [F,3,3], t [F,3], inliers_pts (packed bool [sum P]) with offsets [F+1], inliers_lines (packed bool [sum L]) with
     line_offsets [F+1] on the device; n_inliers (points + lines, a line counting once), status, n_certified, best_index [F] (host, columns
-    of the one read-back `head` [F,4]); sizes, line_sizes, n_hyp.  One host synchronisation per call."""
+    of the one read-back `head` [F,4]); sizes, line_sizes, n_hyp.  One host synchronisation per call.
+    polish=True: as in ransac_pnp_batch, over both consensus masks; the result gains "refine"."""
     ps, ls = _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes)
     F = len(ps)
     if seed is None:
@@ -665,10 +696,14 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
             Bt, Qt, cnt = assemble_pnpl_consensus(sc, mp, ml)
             fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
             refit_update_pnpl_scenes(sc, fit, cnt, thresh, R, t, head, mp, ml)
+    refined = _polish(sc, R, t, head, mp, ml, thresh) if polish else None
     h = head.cpu()   # the call's one synchronisation
-    return {"R": R, "t": t, "inliers_pts": mp.view(torch.bool), "offsets": sc.offsets, "inliers_lines": ml.view(torch.bool),
-            "line_offsets": sc.line_offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3], "best_index": h[:, 2], "head": h,
-            "sizes": sc.sizes, "line_sizes": sc.line_sizes, "n_hyp": int(n_hyp)}
+    out = {"R": R, "t": t, "inliers_pts": mp.view(torch.bool), "offsets": sc.offsets, "inliers_lines": ml.view(torch.bool),
+           "line_offsets": sc.line_offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3], "best_index": h[:, 2], "head": h,
+           "sizes": sc.sizes, "line_sizes": sc.line_sizes, "n_hyp": int(n_hyp)}
+    if polish:
+        out["refine"] = refined
+    return out
 
 
 def ransac_pnl_batch(line_2d, line_3d, K, **kw):
