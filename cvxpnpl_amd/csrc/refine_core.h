@@ -377,7 +377,8 @@ CVX_HD void refine_problem(LN &ln, const double *Kp, const double *Rin, const do
     double cost = NAN, lambda = o.lambda0;
     if (cost_before) *cost_before = NAN;
     int iters = 0;
-    bool active = st < 0, solved = false;
+    bool active = st < 0;
+    int seen = 0; // bit 0 SOLVED: some damped system was positive definite; bit 1 MOVED: some trial was accepted (one value, not two flags: on the device each is a register that lives through the loop)
 
     for (int it = 0;; ++it) {
         const bool run = ln.any(active) && it < o.max_iters; // another trial follows
@@ -389,7 +390,7 @@ CVX_HD void refine_problem(LN &ln, const double *Kp, const double *Rin, const do
         ln.template sum<ACC_N>(acc);
         if (it == 0 && active) {
             cost = acc[27];
-            if (!(cost < INFINITY)) { st = REFINE_BEHIND; active = false; } // (a NaN among the live records ends here too)
+            if (!(cost < INFINITY)) { st = REFINE_BEHIND; active = false; } // (a NaN or inf among the live records' numbers ends here too: the contract, see the header)
             else if (cost_before) *cost_before = cost;
         }
         if (!run) break;
@@ -405,10 +406,11 @@ CVX_HD void refine_problem(LN &ln, const double *Kp, const double *Rin, const do
         ln.template sum<1>(c1);
         if (active) {
             ++iters;
-            solved = solved || ok;
+            seen |= ok ? 1 : 0;
             const bool floor = lambda <= o.lambda0 && fabs(c1[0] - cost) <= COST_TOL * cost; // the two costs agree to their rounding
             if (ok && c1[0] <= cost) { // (a trial with a record behind the camera costs infinity)
                 ps = tr;
+                seen |= 2;
                 cost = c1[0];
                 lambda = lambda * 0.1 > LAMBDA_MIN ? lambda * 0.1 : LAMBDA_MIN;
                 if (rel <= o.step_tol || floor) { st = REFINE_CONVERGED; active = false; }
@@ -416,7 +418,7 @@ CVX_HD void refine_problem(LN &ln, const double *Kp, const double *Rin, const do
                 st = REFINE_CONVERGED; active = false; // (see the header: the rounding floor of the cost)
             } else {
                 lambda *= 10.0;
-                if (lambda > LAMBDA_MAX) { st = solved ? REFINE_MAXITER : REFINE_SINGULAR; active = false; }
+                if (lambda > LAMBDA_MAX) { st = (seen & 1) ? REFINE_MAXITER : REFINE_SINGULAR; active = false; }
             }
         }
     }
@@ -425,7 +427,9 @@ CVX_HD void refine_problem(LN &ln, const double *Kp, const double *Rin, const do
     if (!done && cost_before) *cost_before = NAN; // (lambda ran out before any system was positive definite)
     rot_c(ps, Rc);
     CVX_UNROLL for (int i = 0; i < 9; ++i) res.R[i] = ps.R[i];
-    CVX_UNROLL for (int i = 0; i < 3; ++i) res.t[i] = ps.tc[i] - Rc[i];
+    // (a pose that no trial has moved is the input pose bit for bit -- max_iters = 0, or converged on a rejected trial: (R c + t) - R c is t
+    // only to the rounding of |R c|, so t is read again; nothing has been written by now, the outputs may alias the inputs)
+    CVX_UNROLL for (int i = 0; i < 3; ++i) res.t[i] = (seen & 2) ? ps.tc[i] - Rc[i] : tin[i];
     res.cost = done ? cost : NAN;
     res.iters = done ? iters : 0; res.status = st; res.n_live = n_live;
 }

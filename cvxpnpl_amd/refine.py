@@ -101,8 +101,8 @@ def refine_pose_batch(R, t, pts_2d=None, line_2d=None, pts_3d=None, line_3d=None
     line_3d [B,n_l,2,3] (either pair may be None); K [3,3] or [B,3,3]: contiguous float64 tensors on one GPU.  status [B] int32 (optional;
     a strided column is taken as it is) with admit_mask (bit s: status s is refined; default: the solver's 0 and 2); mask_pts [B,n_p] /
     mask_lines [B,n_l] uint8 (optional, non-zero = live).  Returns a RefineResult of device tensors; nothing is synchronised.
-    status: 0 converged, 1 max_iters, 2 skipped, 3 singular, 4 behind the camera; for 2-4 the pose is the input pose bit for bit and cost
-    and cov are NaN.  cov (want_cov): sigma^2 (J^T J)^-1 at the final pose with sigma^2 = cost_after / (2 n_live - 6), or sigma_px^2."""
+    status: 0 converged, 1 max_iters, 2 skipped, 3 singular, 4 a live record behind the camera or with a non-finite number (NaN / inf in
+    its 2D or 3D half); for 2-4 the pose is the input pose bit for bit and cost and cov are NaN.  cov (want_cov): sigma^2 (J^T J)^-1 at the final pose with sigma^2 = cost_after / (2 n_live - 6), or sigma_px^2."""
     o = _opts(max_iters, step_tol, sigma_px)
     if not isinstance(R, torch.Tensor) or R.dim() != 3:
         raise ValueError("R: expected a torch tensor [B,3,3]")
@@ -140,7 +140,8 @@ def refine_scenes(sc, R, t, mask_pts=None, mask_lines=None, status=None, admit_m
                   want_cov: bool = False, sigma_px: float = 0.0) -> RefineResult:
     """Polish one pose per scene of a packed scene set (``ransac.Scenes`` or ``ransac.PnplScenes``): R [F,3,3], t [F,3]; mask_pts [sum P] /
     mask_lines [sum L] uint8 (optional, non-zero = live: e.g. the consensus masks of the RANSAC layers); status [F] int32 (optional, may be
-    ``head[:, 0]`` of the RANSAC read-back).  One workgroup per scene, one launch, no synchronisation.  Returns a RefineResult."""
+    ``head[:, 0]`` of the RANSAC read-back).  One workgroup per scene, one launch, no synchronisation.  Returns a RefineResult; the
+    statuses are those of ``refine_pose_batch`` (4 also for a non-finite number in a live record)."""
     from . import ransac as _rn
 
     o = _opts(max_iters, step_tol, sigma_px)

@@ -31,9 +31,11 @@ enum {
     CVXPNPL_REFINE_MAXITER = 1,  /* max_iters trials, or lambda beyond 1e12: the cost has not increased, the pose is the best accepted */
     CVXPNPL_REFINE_SKIPPED = 2,  /* input status not in admit_mask, a non-finite pose, or det R <= 0 (a reflection cannot be repaired) */
     CVXPNPL_REFINE_SINGULAR = 3, /* fewer than 3 live correspondences, or no lambda gave a positive definite system */
-    CVXPNPL_REFINE_BEHIND = 4    /* a live record has depth <= 0 (or NaN) at the input pose */
+    CVXPNPL_REFINE_BEHIND = 4    /* a live record has depth <= 0 at the input pose, or holds a number that is not finite (NaN or inf in its
+                                    2D or its 3D half: the cost at the input pose is not a number) */
 };
-/* For statuses 2-4 the output pose is the input pose bit for bit, cost and covariance are NaN, iters is 0. */
+/* For statuses 2-4 the output pose is the input pose bit for bit, cost and covariance are NaN, iters is 0.  With status 0 or 1 a pose that
+ * no trial has moved (max_iters = 0, or converged on a rejected trial) is the input pose bit for bit as well. */
 
 /* Options; NULL means the defaults.  struct_size must be sizeof(cvxpnpl_refine_opts_t): a caller built against another layout is refused. */
 typedef struct {

@@ -29,6 +29,7 @@ def build(force=False):
                                "-o", _SO, srcs[0]])
     build_plan()
     build_recover()
+    build_refine()
     return _SO
 
 
@@ -81,6 +82,56 @@ def recover_lib():
     if _recover_lib is None:
         _recover_lib = C.CDLL(build_recover())
     return _recover_lib
+
+
+_REFINE_SO = os.path.join(_HERE, "librefineshim.so")
+_refine_lib = None
+
+
+def build_refine():
+    """refine_shim.cpp: pose_step, damped_step and step_measure of csrc/refine_core.h behind C entries"""
+    srcs = [os.path.join(_HERE, "refine_shim.cpp"), os.path.join(_CSRC, "refine_core.h"), os.path.join(_CSRC, "problem_io.h")]
+    if not os.path.exists(_REFINE_SO) or os.path.getmtime(_REFINE_SO) < max(os.path.getmtime(s) for s in srcs):
+        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-o", _REFINE_SO, srcs[0]])
+    return _REFINE_SO
+
+
+def refine_lib():
+    global _refine_lib
+    if _refine_lib is None:
+        L = C.CDLL(build_refine())
+        L.rf_pose_step.argtypes = [_dp, _dp, _dp]
+        L.rf_pose_step.restype = None
+        L.rf_damped_step.argtypes = [_dp, C.c_double, _dp]
+        L.rf_damped_step.restype = C.c_int
+        L.rf_step_measure.argtypes = [_dp, _dp, _dp, _dp]
+        L.rf_step_measure.restype = C.c_double
+        _refine_lib = L
+    return _refine_lib
+
+
+def pose_step(R, tc, d):
+    """cvxr::pose_step: (exp([d[:3]]x) R, tc + d[3:])"""
+    R = np.array(R, dtype=np.float64).reshape(9)
+    tc = np.array(tc, dtype=np.float64).reshape(3)
+    d = np.ascontiguousarray(d, dtype=np.float64).reshape(6)
+    refine_lib().rf_pose_step(_p(R), _p(tc), _p(d))
+    return R.reshape(3, 3), tc
+
+
+def damped_step(A, g, lam):
+    """cvxr::damped_step on J^T J = A [6,6] (its upper triangle is read) and J^T r = g [6] -> (ok, d)"""
+    A = np.asarray(A, dtype=np.float64)
+    a = np.concatenate([np.concatenate([A[i, i:] for i in range(6)]), np.asarray(g, dtype=np.float64), [0.0]])
+    d = np.full(6, np.nan)
+    ok = refine_lib().rf_damped_step(_p(a), float(lam), _p(d))
+    return bool(ok), d
+
+
+def step_measure(R, tc, c, d):
+    """cvxr::step_measure at the pose (R, tc) about the centre c"""
+    a = [np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for v in (R, tc, c, d)]
+    return float(refine_lib().rf_step_measure(*[_p(v) for v in a]))
 
 
 def poly_roots(p):

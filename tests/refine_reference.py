@@ -76,31 +76,60 @@ def jacobian(K, R, t, h=1e-3, **data):
     return np.stack(cols, 1).astype(np.float64)
 
 
-def lm_step(K, R, t, lam=LAMBDA0, **data):
+def far_h(**data):
+    """The difference step for a scene far from the world origin: 1e-3 / (1 + max |X| over the live 3D records).  A rotation of h about
+    the world origin moves a point at distance |X| by h |X|: with the fixed 1e-3 and points 100 units out, the residuals are sampled over
+    a range on which the sixth-order formula no longer holds (the reference then reports a next step of 3.6e-3 from a converged pose)."""
+    lp, ll = live_sets(data.get("pts_2d"), data.get("line_2d"), data.get("mask_pts"), data.get("mask_lines"))
+    big = 0.0
+    with np.errstate(invalid="ignore"):
+        if lp.any():
+            big = max(big, float(np.abs(np.asarray(data["pts_3d"], float)[lp]).max()))
+        if ll.any():
+            big = max(big, float(np.abs(np.asarray(data["line_3d"], float)[ll]).max()))
+    return 1e-3 / (1.0 + big)
+
+
+def live_data_finite(**data):
+    """True when every number of a live record (its 2D and its 3D half) is finite."""
+    lp, ll = live_sets(data.get("pts_2d"), data.get("line_2d"), data.get("mask_pts"), data.get("mask_lines"))
+    ok = True
+    if lp.any():
+        ok = ok and np.isfinite(np.asarray(data["pts_2d"], float)[lp]).all() and np.isfinite(np.asarray(data["pts_3d"], float)[lp]).all()
+    if ll.any():
+        ok = ok and np.isfinite(np.asarray(data["line_2d"], float)[ll]).all() and np.isfinite(np.asarray(data["line_3d"], float)[ll]).all()
+    return bool(ok)
+
+
+def lm_step(K, R, t, lam=LAMBDA0, h=1e-3, **data):
     """The step the schedule takes from (R, t) at damping lam: (J^T J + lam diag(J^T J)) d = -J^T r.  Returns (d, J^T J, r)."""
     r, _ = residuals(K, R, t, **data)
-    J = jacobian(K, R, t, **data)
+    J = jacobian(K, R, t, h=h, **data)
     A = J.T @ J
     d = np.linalg.solve(A + lam * np.diag(np.diag(A)), -J.T @ r)
     return d, A, r
 
 
-def refine(K, R, t, max_iters=30, step_tol=1e-10, **data):
-    """The schedule of refine_core.h on one problem.  Returns dict(R, t, cost (before, after), iters, status, history of costs)."""
+def refine(K, R, t, max_iters=30, step_tol=1e-10, h=1e-3, **data):
+    """The schedule of refine_core.h on one problem.  Returns dict(R, t, cost (before, after), iters, status, history of costs, rejected:
+    the number of rejected trials, behind_trials: those of them whose trial pose had a live record at depth <= 0).  A pose that is not
+    refined (status >= 2) is the input pose; a non-finite number in a live record is status 4, as a record behind the camera is."""
     R, t = np.array(R, float), np.array(t, float)
-    r, zmin = residuals(K, R, t, **data)
+    with np.errstate(invalid="ignore", over="ignore"):
+        r, zmin = residuals(K, R, t, **data)
+    skip = {"R": R, "t": t, "cost": (np.nan, np.nan), "iters": 0, "rejected": 0, "behind_trials": 0}
     lp, ll = live_sets(data.get("pts_2d"), data.get("line_2d"), data.get("mask_pts"), data.get("mask_lines"))
     if not np.all(np.isfinite(R)) or not np.all(np.isfinite(t)) or not np.linalg.det(R) > 0:
-        return {"R": R, "t": t, "cost": (np.nan, np.nan), "iters": 0, "status": 2}
+        return dict(skip, status=2)
     if lp.sum() + ll.sum() < 3:
-        return {"R": R, "t": t, "cost": (np.nan, np.nan), "iters": 0, "status": 3}
-    if not zmin > 0:
-        return {"R": R, "t": t, "cost": (np.nan, np.nan), "iters": 0, "status": 4}
+        return dict(skip, status=3)
+    if not live_data_finite(**data) or not zmin > 0:
+        return dict(skip, status=4)
     cost0 = cost = float(r @ r)
-    lam, iters, status, hist = LAMBDA0, 0, 1, [cost]
+    lam, iters, status, hist, rejected, behind = LAMBDA0, 0, 1, [cost], 0, 0
     while iters < max_iters:
         iters += 1
-        d, _, _ = lm_step(K, R, t, lam, **data)
+        d, _, _ = lm_step(K, R, t, lam, h=h, **data)
         Rn, tn = expm_so3(d[:3]) @ R, t + d[3:]
         rn, zn = residuals(K, Rn, tn, **data)
         small = np.linalg.norm(d) <= step_tol * (1.0 + np.linalg.norm(t))
@@ -116,14 +145,16 @@ def refine(K, R, t, max_iters=30, step_tol=1e-10, **data):
             status = 0
             break
         else:
+            rejected += 1
+            behind += int(not zn > 0)
             lam *= 10.0
             if lam > LAMBDA_MAX:
                 break
-    return {"R": R, "t": t, "cost": (cost0, cost), "iters": iters, "status": status, "history": hist}
+    return {"R": R, "t": t, "cost": (cost0, cost), "iters": iters, "status": status, "history": hist, "rejected": rejected, "behind_trials": behind}
 
 
-def covariance(K, R, t, sigma2, **data):
+def covariance(K, R, t, sigma2, h=1e-3, **data):
     """sigma2 (J^T J)^-1 at (R, t) in the public chart, and J^T J itself."""
-    J = jacobian(K, R, t, **data)
+    J = jacobian(K, R, t, h=h, **data)
     A = J.T @ J
     return sigma2 * np.linalg.inv(A), A

@@ -77,7 +77,8 @@ def test_covariance_on_the_device(shape, sigma_px):
 
 
 def test_status_column_and_in_place_output():
-    """A strided status column is read as it is (head[:, 0] of the RANSAC read-back), and admit_mask selects."""
+    """A strided status column is read as it is (head[:, 0] of the RANSAC read-back), admit_mask selects, and the outputs may be the
+    inputs' own arrays."""
     from cvxpnpl_amd import refine as rf
 
     d, R0, t0, kw = rc.problem(9, 10, 0, 1.0)
@@ -87,6 +88,23 @@ def test_status_column_and_in_place_output():
     res = rf.refine_pose_batch(_dev(R0), _dev(t0), pts_2d=_dev(kw["pts_2d"]), pts_3d=_dev(kw["pts_3d"]), K=_dev(d["K"]), status=head[:, 0])
     st = res.status.cpu().numpy()
     assert st[2] == 2 and (np.delete(st, 2) <= 1).all()
+    # in place: the C entry with d_R_out = d_R and d_t_out = d_t (the Python wrapper always allocates), the same strided column
+    import ctypes as C
+
+    from cvxpnpl_amd import _lib
+
+    def ptr(x):
+        return C.c_void_p(x.data_ptr())
+
+    R, t, p2, p3, K = _dev(R0), _dev(t0), _dev(kw["pts_2d"]), _dev(kw["pts_3d"]), _dev(d["K"])
+    _, _, cost, iters, ost, n_live, _ = rf._outputs(9, R.device, False)
+    code = _lib.refine_lib().cvxpnpl_refine_batch(9, 10, ptr(p2), ptr(p3), 0, None, None, ptr(K), 0, ptr(R), ptr(t), ptr(head), 4, rf.ADMIT_USABLE, None, None,
+                                                  None, ptr(R), ptr(t), ptr(cost), ptr(iters), ptr(ost), ptr(n_live), None,
+                                                  C.c_void_p(torch.cuda.current_stream().cuda_stream))
+    assert code == 0
+    for got, want in ((R, res.R), (t, res.t), (cost, res.cost), (iters, res.iters), (ost, res.status), (n_live, res.n_live)):
+        assert got.cpu().numpy().tobytes() == want.cpu().numpy().tobytes()
+    assert R[2].cpu().numpy().tobytes() == R0[2].tobytes() and t[2].cpu().numpy().tobytes() == t0[2].tobytes()   # the skipped one: bit for bit
     res = rf.refine_pose_batch(_dev(R0), _dev(t0), pts_2d=_dev(kw["pts_2d"]), pts_3d=_dev(kw["pts_3d"]), K=_dev(d["K"]), status=head[:, 0], admit_mask=0x1)
     assert res.status.cpu().numpy()[[2, 5]].tolist() == [2, 2]
 
