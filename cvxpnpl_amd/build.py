@@ -80,13 +80,28 @@ REFINE_SRC = os.path.join(HERE, "csrc", "refine_hip.hip")
 REFINE_HOST_SRC = os.path.join(HERE, "csrc", "host_refine.cpp")
 REFINE_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine.so")
 REFINE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine.resources.txt")
-REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"),
+REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"), os.path.join(HERE, "csrc", "refine_lanes.h"),
                os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine.h")]
 
 
 def refine_compile_cmd(out=REFINE_OUT):
     return grad_compile_cmd(out)[:-2] + [REFINE_SRC, REFINE_HOST_SRC]
+
+
+# the backward pass of the refinement (include/cvxpnpl_amd_refine_grad.h): the sixth library, the flags of the second and the fifth
+REFINE_GRAD_SRC = os.path.join(HERE, "csrc", "refine_grad_hip.hip")
+REFINE_GRAD_HOST_SRC = os.path.join(HERE, "csrc", "host_refine_vjp.cpp")
+REFINE_GRAD_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine_grad.so")
+REFINE_GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_grad.resources.txt")
+REFINE_GRAD_DEPS = [REFINE_GRAD_SRC, REFINE_GRAD_HOST_SRC, os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_vjp_kernel.h"),
+                    os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                    os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                    os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_grad.h")]
+
+
+def refine_grad_compile_cmd(out=REFINE_GRAD_OUT):
+    return grad_compile_cmd(out)[:-2] + [REFINE_GRAD_SRC, REFINE_GRAD_HOST_SRC]
 
 
 def _build_one(out, resources, deps, cmd, force, verbose):
@@ -123,13 +138,18 @@ def build_refine(force=False, verbose=False):
     return _build_one(REFINE_OUT, REFINE_RESOURCES, REFINE_DEPS, refine_compile_cmd(), force, verbose)
 
 
+def build_refine_grad(force=False, verbose=False):
+    return _build_one(REFINE_GRAD_OUT, REFINE_GRAD_RESOURCES, REFINE_GRAD_DEPS, refine_grad_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All five libraries; returns the solver's (OUT)."""
+    """All six libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
     build_ransac_pnpl(force, verbose)
     build_refine(force, verbose)
+    build_refine_grad(force, verbose)
     return OUT
 
 
