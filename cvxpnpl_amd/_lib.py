@@ -294,6 +294,45 @@ def refine_grad_lib():
     return L
 
 
+# the refinement under a robust loss and weights (include/cvxpnpl_amd_refine_robust.h): the seventh library
+REFINE_ROBUST_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_refine_robust.so")
+REFINE_ROBUST_EXPORTS = ("cvxpnpl_refine_robust_batch", "cvxpnpl_refine_robust_scenes", "cvxpnpl_refine_robust_batch_host",
+                         "cvxpnpl_refine_robust_last_error", "cvxpnpl_refine_robust_version")
+LOSS_L2, LOSS_HUBER, LOSS_CAUCHY = 0, 1, 2  # CVXPNPL_LOSS_*
+LOSS_NAMES = {"l2": LOSS_L2, "huber": LOSS_HUBER, "cauchy": LOSS_CAUCHY}
+
+
+class RefineRobustOpts(C.Structure):
+    """cvxpnpl_refine_robust_opts_t"""
+    _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("step_tol", C.c_double), ("lambda0", C.c_double), ("loss", C.c_int32),
+                ("scale_px", C.c_double)]
+
+
+_refine_robust_lib = None
+
+
+def refine_robust_lib():
+    """Load libcvxpnpl_amd_refine_robust.so (loudly)."""
+    global _refine_robust_lib
+    if _refine_robust_lib is not None:
+        return _refine_robust_lib
+    if not os.path.exists(REFINE_ROBUST_LIB_PATH):
+        raise LibraryMissing(f"{REFINE_ROBUST_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(REFINE_ROBUST_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    pose = [p, i32, p, p, p, i64, C.c_uint32, p, p, p, p, C.POINTER(RefineRobustOpts)]  # K, K_per, R, t, status, stride, admit, masks, weights, opts
+    outs = [p, p, p, p, p, p]                                                          # R, t, cost, iters, status, n_live
+    L.cvxpnpl_refine_robust_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [p, p, p]         # robust_w, n_inlier, stream
+    L.cvxpnpl_refine_robust_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [p, p, i32]  # robust_w, n_inlier, n_threads
+    L.cvxpnpl_refine_robust_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + outs + [p, p, p, p]  # robust_w_pts, robust_w_lines, n_inlier, stream
+    for name in REFINE_ROBUST_EXPORTS[:3]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_refine_robust_last_error.restype = C.c_char_p
+    L.cvxpnpl_refine_robust_version.restype = C.c_char_p
+    _refine_robust_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))
