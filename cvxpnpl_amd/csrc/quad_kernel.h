@@ -233,16 +233,28 @@ struct Own {
 // direction space (tgt = 0); closed form of cvx::proj_affine.
 // VAR_RC (the reference's "rc" ablation, benchmarks/toolkit/methods/rc.py:9-64): the row-orthonormality rows are absent -- the entries
 // inside one diagonal 3x3 block (triples 0..2) are free and a diagonal entry only sees its column sum (cvxw::coop_proj).
-template <int VAR = cvx::VAR_FULL, class OWN>
+// AHEAD: the partner entries are read with the diagonal instead of where they are used (see below).  The float64-sweep instantiations only: in
+// the single-precision ones any of the round-8 read-ahead edits leaves an unused 64 B slot in the frame (scratch 124 -> 188 B per lane for
+// <0,2,16,false,0>), which tests/test_kernel_resources.py does not allow -- they keep the code they had, here and in the W+ loop.
+template <int VAR = cvx::VAR_FULL, bool AHEAD = false, class OWN>
 __device__ __forceinline__ void quad_proj(double *L, const OWN &w, double *X, double tgt)
 {
 #pragma unroll
     for (int m = 0; m < OWN::EPL; ++m)
         if (w.ok(m)) L[Q_X + w.e(m)] = X[m];
     CVXW_SYNC();
-    double d[9];
+    double d[9], x1[OWN::EPL], x2[OWN::EPL];
 #pragma unroll
     for (int k = 0; k < 9; ++k) d[k] = L[Q_X + cvx::sidx(k, k)];
+    // The two partner entries of every owned entry are read HERE, with the diagonal: 9 + 2 EPL independent reads in flight behind the one fence.
+    // Read where they are used, the compiler sank each pair into the EXEC-masked arm of its entry's select and waited on it there -- EPL LDS
+    // round trips in a row (profiles/r08/quad_lds_phases_ab.txt).  The empty asm is what keeps them out of those arms.
+    if constexpr (AHEAD) {
+#pragma unroll
+        for (int m = 0; m < OWN::EPL; ++m) { x1[m] = L[Q_X + ((w.pk[m] >> 8) & 63)]; x2[m] = L[Q_X + ((w.pk[m] >> 14) & 63)]; }
+#pragma unroll
+        for (int m = 0; m < OWN::EPL; ++m) asm volatile("" : "+v"(x1[m]), "+v"(x2[m]));
+    }
     const double r0 = d[0] + d[3] + d[6] - tgt, r1 = d[1] + d[4] + d[7] - tgt, r2 = d[2] + d[5] + d[8] - tgt;
     const double c0 = d[0] + d[1] + d[2] - tgt, c1 = d[3] + d[4] + d[5] - tgt, c2 = d[6] + d[7] + d[8] - tgt;
     const double tot = r0 + r1 + r2;
@@ -252,9 +264,9 @@ __device__ __forceinline__ void quad_proj(double *L, const OWN &w, double *X, do
         const int ri = w.ei(m) % 3, ci = w.ei(m) / 3; // diagonal entry (ei, ei), ei < 9, is D[ri][ci]
         const double rr = ri == 0 ? r0 : (ri == 1 ? r1 : r2), cc = ci == 0 ? c0 : (ci == 1 ? c1 : c2);
         const double xdiag = (w.ei(m) == 9) ? tgt : X[m] - (VAR == cvx::VAR_RC ? cc * (1.0 / 3.0) : (rr + cc) * (1.0 / 3.0) - tot * (1.0 / 9.0));
-        const double x1 = L[Q_X + ((pk >> 8) & 63)], x2 = L[Q_X + ((pk >> 14) & 63)];
+        if constexpr (!AHEAD) { x1[m] = L[Q_X + ((pk >> 8) & 63)]; x2[m] = L[Q_X + ((pk >> 14) & 63)]; }
         const unsigned n0 = (pk >> 20) & 1;
-        const double mm = (flip(X[m], n0) + flip(x1, (pk >> 21) & 1) + flip(x2, (pk >> 22) & 1)) * (1.0 / 3.0);
+        const double mm = (flip(X[m], n0) + flip(x1[m], (pk >> 21) & 1) + flip(x2[m], (pk >> 22) & 1)) * (1.0 / 3.0);
         const bool free_entry = VAR == cvx::VAR_RC && w.ei(m) != w.ej(m) && w.ej(m) < 9 && (w.ei(m) / 3 == w.ej(m) / 3);
         X[m] = ((pk >> 23) & 1) ? xdiag : (free_entry ? X[m] : X[m] - flip(mm, n0));
     }
@@ -304,7 +316,9 @@ __device__ __forceinline__ void pair_cs_f64(double d, double gam, bool rot, bool
 #endif
     const double u = h + fabs(d);
     const double w = cvx::rsqrt_(fma(u, u, g22));
-    const bool neg = d < 0.0 || (d == 0.0 && tie_neg);
+    // (compare, compare, and, or: '||' compiled to an EXEC-masked branch in every step.  pair_cs keeps '||': without the branch the compiler
+    //  packs d d with g2 g2 into one v_pk_mul_f32 and no longer contracts h2 -- other bits; profiles/r08/quad_lds_phases_ab.txt)
+    const bool neg = (d < 0.0) | ((d == 0.0) & tie_neg);
     const double sf = (neg ? -g2 : g2) * w;
     c = rot ? u * w : 1.0;
     s = rot ? sf : 0.0;
@@ -860,14 +874,36 @@ __global__ void __launch_bounds__(64, OCC) solve_quad_kernel(QuadArgs k)
                 for (int m = 0; m < EPL; ++m)
                     if (w.ok(m)) { L[Q_WF + w.ei(m) * 10 + w.ej(m)] = W[m]; L[Q_WF + w.ej(m) * 10 + w.ei(m)] = W[m]; }
                 CVXW_SYNC();
+                // Row i is the chain fma(W[i][k], vd[k], .) over k = 0 ... 9 from 0, then fma(sigma, vd[i], .) -- that order is the result's bits and stays.
+                // What is scheduled is the ten rows AGAINST each other: column pair kk of all ten rows is one stage of ten b128 reads and twenty FMAs
+                // on ten independent chains, and the reads run two stages ahead of their use (20 in flight at the start, 10 behind every stage).
+                // Row by row, as this was written until round 8, each row was one dependent chain (8 cycles per float64 FMA) behind two or three
+                // reads in flight, and a lone wavefront has nothing to hide either behind (profiles/r08/quad_lds_phases_ab.txt).  The sched_barriers
+                // keep the stages apart: left alone, the scheduler folds them back into rows to save the 80 registers -- which are free here
+                // (Wp, the attempt's temporaries and the previous qd are dead).
                 double qd[10];
+                {
+                    const double2 *wf = L2 + Q_WF / 2;
+                    double2 r[2][10];
 #pragma unroll
-                for (int i = 0; i < 10; ++i) {
-                    const double2 *row = L2 + (Q_WF + i * 10) / 2;
-                    double a = 0.0;
+                    for (int i = 0; i < 10; ++i) r[0][i] = wf[i * 5];
 #pragma unroll
-                    for (int kk = 0; kk < 5; ++kk) { const double2 r = row[kk]; a = fma(r.x, vd[2 * kk], a); a = fma(r.y, vd[2 * kk + 1], a); }
-                    qd[i] = fma(sigma, vd[i], a);
+                    for (int i = 0; i < 10; ++i) r[1][i] = wf[i * 5 + 1];
+#pragma unroll
+                    for (int kk = 0; kk < 5; ++kk) {
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int i = 0; i < 10; ++i) qd[i] = fma(r[kk & 1][i].x, vd[2 * kk], kk == 0 ? 0.0 : qd[i]);
+#pragma unroll
+                        for (int i = 0; i < 10; ++i) qd[i] = fma(r[kk & 1][i].y, vd[2 * kk + 1], qd[i]);
+                        if (kk + 2 < 5) {
+#pragma unroll
+                            for (int i = 0; i < 10; ++i) r[kk & 1][i] = wf[i * 5 + kk + 2];
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < 10; ++i) qd[i] = fma(sigma, vd[i], qd[i]);
                 }
                 double alq = dot10_f64(qd, qd);
 CVXQ_PH(0);
@@ -971,12 +1007,49 @@ CVXQ_PH(1); /* jacobi */
             CVXW_SYNC();
 #pragma unroll
             for (int m = 0; m < EPL; ++m) Wp[m] = 0.0;
+            // The columns with weight in ANY problem of the wavefront (wave-uniform; one without weight in THIS problem adds 0), in ascending order,
+            // the others skipped.  Two register sets: the 1 + 2 EPL reads of the next such column are in flight while the current one is consumed
+            // (until round 8 every column was read and waited on in its own block).  Per term (ws a) b and then the add, as one fma -- what the
+            // compiler made of "Wp += ws * a * b"; written out so that it stays that.
+            if constexpr (F64SW) {
+                unsigned rem = (unsigned)__builtin_amdgcn_readfirstlane((int)anypos);
+                double wa, aa[EPL], ba[EPL], wb, ab[EPL], bb[EPL];
+                auto rd = [&](double &ws_, double (&a_)[EPL], double (&b_)[EPL]) {
+                    const int s = __builtin_ctz(rem);
+                    rem &= rem - 1u;
+                    const double *c = L + Q_Y + s * 10;
+                    ws_ = L[Q_Y + 100 + s];
 #pragma unroll
-            for (int s = 0; s < 10; ++s) {
-                if ((anypos >> s) & 1u) { // wave-uniform; a column with no weight in THIS problem adds 0
-                    const double ws_ = L[Q_Y + 100 + s];
+                    for (int m = 0; m < EPL; ++m) { a_[m] = c[w.ei(m)]; b_[m] = c[w.ej(m)]; }
+                };
+                auto add = [&](double ws_, const double (&a_)[EPL], const double (&b_)[EPL]) {
 #pragma unroll
-                    for (int m = 0; m < EPL; ++m) Wp[m] += ws_ * L[Q_Y + s * 10 + w.ei(m)] * L[Q_Y + s * 10 + w.ej(m)];
+                    for (int m = 0; m < EPL; ++m) Wp[m] = fma(ws_ * a_[m], b_[m], Wp[m]);
+                };
+                if (rem) {
+                    rd(wa, aa, ba);
+                    // (unrolled, no back edge: around a loop the wait-count insertion drains the counter at the header, and the read-ahead with it;
+                    //  anypos has ten bits, so the fifth pass ends with the tenth column at the latest)
+#pragma unroll
+                    for (int p = 0; p < 5; ++p) {
+                        if (!rem) { add(wa, aa, ba); break; }
+                        rd(wb, ab, bb);
+                        __builtin_amdgcn_sched_barrier(0);
+                        add(wa, aa, ba);
+                        if (p == 4 || !rem) { add(wb, ab, bb); break; }
+                        rd(wa, aa, ba);
+                        __builtin_amdgcn_sched_barrier(0);
+                        add(wb, ab, bb);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 10; ++s) {
+                    if ((anypos >> s) & 1u) {
+                        const double ws_ = L[Q_Y + 100 + s];
+#pragma unroll
+                        for (int m = 0; m < EPL; ++m) Wp[m] += ws_ * L[Q_Y + s * 10 + w.ei(m)] * L[Q_Y + s * 10 + w.ej(m)];
+                    }
                 }
             }
         }
@@ -1137,7 +1210,7 @@ CVXQ_PH(4); /* polar + Newton polish */
                 double T[EPL];
 #pragma unroll
                 for (int m = 0; m < EPL; ++m) { S[m] = rho * (Wp[m] - W[m]); T[m] = S[m] - (w.ej(m) < 9 ? L[Q_QF + w.ei(m) * 10 + w.ej(m)] : 0.0); }
-                quad_proj<VAR>(L, w, T, 0.0);
+                quad_proj<VAR, F64SW>(L, w, T, 0.0);
 #pragma unroll
                 for (int m = 0; m < EPL; ++m) {
                     S[m] = odd[m] ? 0.0 : S[m] - T[m];
@@ -1165,7 +1238,7 @@ CVXQ_PH(4); /* polar + Newton polish */
                     E[m] = odd[m] ? 0.0 : 0.5 * (L[C_LAM + w.ei(m)] * L[C_XV + w.ej(m)] + L[C_XV + w.ei(m)] * L[C_LAM + w.ej(m)]);
                     Nn[m] = E[m];
                 }
-                quad_proj<VAR>(L, w, Nn, 0.0);
+                quad_proj<VAR, F64SW>(L, w, Nn, 0.0);
 #pragma unroll
                 for (int m = 0; m < EPL; ++m) {
                     S[m] -= E[m] - Nn[m];
@@ -1241,7 +1314,7 @@ CVXQ_PH(6); /* LDL + outputs (or nothing when no check) */
             double X[EPL];
 #pragma unroll
             for (int m = 0; m < EPL; ++m) X[m] = 2.0 * Wp[m] - W[m] - irho * (w.ej(m) < 9 ? L[Q_QF + w.ei(m) * 10 + w.ej(m)] : 0.0); // (the cost entries stay in LDS: 8 registers less to carry through the loop)
-            quad_proj<VAR>(L, w, X, 1.0);
+            quad_proj<VAR, F64SW>(L, w, X, 1.0);
             double r2 = 0.0;
 #pragma unroll
             for (int m = 0; m < EPL; ++m) {
@@ -1249,6 +1322,8 @@ CVXQ_PH(6); /* LDL + outputs (or nothing when no check) */
                 W[m] += o.alpha * dd;
                 r2 += w.wgt(m) * dd * dd;
             }
+            // (Guard: fp_res is NaN exactly when the sum is +inf -- sqrt_fast is x > 0 ? x rsqrt_(x) : 0, so a NaN sum gives 0 and passes here; the
+            //  certificate attempt and the hand-over see those.  Replacing it by a NaN ballot of r2 would decide differently: not done.)
             const double fp_res = cvx::sqrt_fast(grp_sum<LPP>(L, gl, r2));
             if (!done && !(fp_res == fp_res)) { // NaN guard
                 if (gl < 9) a.R[b * 9 + gl] = NAN;
