@@ -333,6 +333,36 @@ def refine_robust_lib():
     return L
 
 
+# the backward pass of the robust refinement (include/cvxpnpl_amd_refine_robust_grad.h): the eighth library
+REFINE_ROBUST_GRAD_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_refine_robust_grad.so")
+REFINE_ROBUST_GRAD_EXPORTS = ("cvxpnpl_refine_robust_vjp_batch", "cvxpnpl_refine_robust_vjp_scenes", "cvxpnpl_refine_robust_vjp_batch_host",
+                              "cvxpnpl_refine_robust_grad_last_error", "cvxpnpl_refine_robust_grad_version")
+
+_refine_robust_grad_lib = None
+
+
+def refine_robust_grad_lib():
+    """Load libcvxpnpl_amd_refine_robust_grad.so (loudly)."""
+    global _refine_robust_grad_lib
+    if _refine_robust_grad_lib is not None:
+        return _refine_robust_grad_lib
+    if not os.path.exists(REFINE_ROBUST_GRAD_LIB_PATH):
+        raise LibraryMissing(f"{REFINE_ROBUST_GRAD_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(REFINE_ROBUST_GRAD_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    pose = [p, i32, p, p, p, i64, C.c_uint32, i32, C.c_double, p, p, p, p]  # K, K_per, R, t, refine status, stride, admit, loss, scale_px, masks, weights
+    grads = [p, p, p, p, p, p, p, p, p, p]  # grad_R, grad_t, g_pts_2d, g_pts_3d, g_line_2d, g_line_3d, g_w_pts, g_w_lines, vjp_status, info
+    L.cvxpnpl_refine_robust_vjp_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + grads + [p]
+    L.cvxpnpl_refine_robust_vjp_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + grads + [i32]
+    L.cvxpnpl_refine_robust_vjp_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + grads + [p]
+    for name in REFINE_ROBUST_GRAD_EXPORTS[:3]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_refine_robust_grad_last_error.restype = C.c_char_p
+    L.cvxpnpl_refine_robust_grad_version.restype = C.c_char_p
+    _refine_robust_grad_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -119,6 +119,23 @@ def refine_robust_compile_cmd(out=REFINE_ROBUST_OUT):
     return grad_compile_cmd(out)[:-2] + [REFINE_ROBUST_SRC, REFINE_ROBUST_HOST_SRC]
 
 
+# the backward pass of the robust refinement (include/cvxpnpl_amd_refine_robust_grad.h): the eighth library, the flags of the fifth to seventh
+REFINE_ROBUST_GRAD_SRC = os.path.join(HERE, "csrc", "refine_robust_grad_hip.hip")
+REFINE_ROBUST_GRAD_HOST_SRC = os.path.join(HERE, "csrc", "host_refine_robust_vjp.cpp")
+REFINE_ROBUST_GRAD_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine_robust_grad.so")
+REFINE_ROBUST_GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_robust_grad.resources.txt")
+REFINE_ROBUST_GRAD_DEPS = [REFINE_ROBUST_GRAD_SRC, REFINE_ROBUST_GRAD_HOST_SRC, os.path.join(HERE, "csrc", "refine_robust_vjp_core.h"),
+                           os.path.join(HERE, "csrc", "refine_robust_vjp_kernel.h"), os.path.join(HERE, "csrc", "refine_robust_core.h"),
+                           os.path.join(HERE, "csrc", "refine_robust_kernel.h"), os.path.join(HERE, "csrc", "refine_vjp_core.h"),
+                           os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                           os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                           os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust_grad.h")]
+
+
+def refine_robust_grad_compile_cmd(out=REFINE_ROBUST_GRAD_OUT):
+    return grad_compile_cmd(out)[:-2] + [REFINE_ROBUST_GRAD_SRC, REFINE_ROBUST_GRAD_HOST_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -161,8 +178,12 @@ def build_refine_robust(force=False, verbose=False):
     return _build_one(REFINE_ROBUST_OUT, REFINE_ROBUST_RESOURCES, REFINE_ROBUST_DEPS, refine_robust_compile_cmd(), force, verbose)
 
 
+def build_refine_robust_grad(force=False, verbose=False):
+    return _build_one(REFINE_ROBUST_GRAD_OUT, REFINE_ROBUST_GRAD_RESOURCES, REFINE_ROBUST_GRAD_DEPS, refine_robust_grad_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All seven libraries; returns the solver's (OUT)."""
+    """All eight libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -170,6 +191,7 @@ def build(force=False, verbose=False):
     build_refine(force, verbose)
     build_refine_grad(force, verbose)
     build_refine_robust(force, verbose)
+    build_refine_robust_grad(force, verbose)
     return OUT
 
 
