@@ -363,6 +363,39 @@ def refine_robust_grad_lib():
     return L
 
 
+# adaptive RANSAC, a hypothesis budget per scene solved in rounds (include/cvxpnpl_amd_ransac_adaptive.h): the ninth library
+RANSAC_ADAPTIVE_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_adaptive.so")
+RANSAC_ADAPTIVE_EXPORTS = ("cvxpnpl_ransac_adaptive_init", "cvxpnpl_ransac_adaptive_sample", "cvxpnpl_ransac_adaptive_score",
+                           "cvxpnpl_ransac_adaptive_update", "cvxpnpl_ransac_adaptive_compact", "cvxpnpl_ransac_adaptive_needed_host",
+                           "cvxpnpl_ransac_adaptive_last_error")
+
+_ransac_adaptive_lib = None
+
+
+def ransac_adaptive_lib():
+    """Load libcvxpnpl_amd_ransac_adaptive.so (loudly)."""
+    global _ransac_adaptive_lib
+    if _ransac_adaptive_lib is not None:
+        return _ransac_adaptive_lib
+    if not os.path.exists(RANSAC_ADAPTIVE_LIB_PATH):
+        raise LibraryMissing(f"{RANSAC_ADAPTIVE_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(RANSAC_ADAPTIVE_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.cvxpnpl_ransac_adaptive_init.argtypes = [i64, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_adaptive_sample.argtypes = [i64, i64, p, i32, i32, i32, p, i64, p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_adaptive_score.argtypes = [i64, i64, p, i32, p, i64, p, p, p, C.c_uint32, p, i32, p, p, C.c_double, p, p]
+    L.cvxpnpl_ransac_adaptive_update.argtypes = [i64, i64, p, i32, i32, i32, C.c_double, p, i64, p, p, p, p, p, i32, p, p, C.c_double,
+                                                 p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_adaptive_compact.argtypes = [i64, i64, p, p, p, p, p]
+    for name in RANSAC_ADAPTIVE_EXPORTS[:5]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_ransac_adaptive_needed_host.argtypes = [i32, i32, C.c_double]
+    L.cvxpnpl_ransac_adaptive_needed_host.restype = C.c_double
+    L.cvxpnpl_ransac_adaptive_last_error.restype = C.c_char_p
+    _ransac_adaptive_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

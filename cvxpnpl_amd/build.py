@@ -136,6 +136,19 @@ def refine_robust_grad_compile_cmd(out=REFINE_ROBUST_GRAD_OUT):
     return grad_compile_cmd(out)[:-2] + [REFINE_ROBUST_GRAD_SRC, REFINE_ROBUST_GRAD_HOST_SRC]
 
 
+# adaptive RANSAC, a hypothesis budget per scene solved in rounds (include/cvxpnpl_amd_ransac_adaptive.h): the ninth library, the flags of
+# the third
+RANSAC_ADAPTIVE_SRC = os.path.join(HERE, "csrc", "ransac_adaptive_hip.hip")
+RANSAC_ADAPTIVE_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_adaptive.so")
+RANSAC_ADAPTIVE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_adaptive.resources.txt")
+RANSAC_ADAPTIVE_DEPS = [RANSAC_ADAPTIVE_SRC, os.path.join(HERE, "csrc", "ransac_adaptive_kernel.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
+                        os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_adaptive.h")]
+
+
+def ransac_adaptive_compile_cmd(out=RANSAC_ADAPTIVE_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_ADAPTIVE_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -182,8 +195,12 @@ def build_refine_robust_grad(force=False, verbose=False):
     return _build_one(REFINE_ROBUST_GRAD_OUT, REFINE_ROBUST_GRAD_RESOURCES, REFINE_ROBUST_GRAD_DEPS, refine_robust_grad_compile_cmd(), force, verbose)
 
 
+def build_ransac_adaptive(force=False, verbose=False):
+    return _build_one(RANSAC_ADAPTIVE_OUT, RANSAC_ADAPTIVE_RESOURCES, RANSAC_ADAPTIVE_DEPS, ransac_adaptive_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All eight libraries; returns the solver's (OUT)."""
+    """All nine libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -192,6 +209,7 @@ def build(force=False, verbose=False):
     build_refine_grad(force, verbose)
     build_refine_robust(force, verbose)
     build_refine_robust_grad(force, verbose)
+    build_ransac_adaptive(force, verbose)
     return OUT
 
 

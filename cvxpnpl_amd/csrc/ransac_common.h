@@ -1,11 +1,15 @@
 // ransac_common.h -- what the two RANSAC libraries share (libcvxpnpl_amd_ransac.so: ransac_kernel.h, points; libcvxpnpl_amd_ransac_pnpl.so:
 // ransac_pnpl_kernel.h, points and lines): the clamped slice of a scene, the Philox generator of the samplers and the point inlier
-// predicate.  ONE definition of each, and no kernel: a library that includes this header compiles nothing it does not launch.
+// predicate.  ONE definition of each (block_inliers, the mask of one pose by a workgroup of SCENE_BLOCK lanes, among them: the selection and refit
+// kernels of ransac_kernel.h and the round update of ransac_adaptive_kernel.h write their masks with it), and no kernel: a library that includes this header compiles nothing it does not launch.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace cvxn {
+
+constexpr int SCENE_BLOCK = 256;  // lanes of the sampling / scoring / selection / refit workgroups
+constexpr int SCENE_WAVES = SCENE_BLOCK / 64;
 
 struct Slice { int64_t beg; int32_t n; };
 __device__ inline Slice scene_slice(const int64_t *off, int64_t f, int64_t n_total)
@@ -47,6 +51,25 @@ __device__ inline bool is_inlier(const Camera &c, double X, double Y, double Z, 
     const double depth = c.r2[0] * X + c.r2[1] * Y + c.r2[2] * Z + c.t2;
     const double du = u / w - x, dv = v / w - y;
     return depth > 0.0 && (du * du + dv * dv < th2);
+}
+
+// inliers of ONE pose over one scene, by the lanes of one workgroup: writes mask (optional) and returns the count to every lane
+__device__ inline int block_inliers(const Camera &cam, int n, const double *s2, const double *s3, double th2, uint8_t *mask, int *red /* LDS, SCENE_WAVES ints */)
+{
+    int cnt = 0;
+    for (int m = threadIdx.x; m < n; m += SCENE_BLOCK) {
+        const bool in = is_inlier(cam, s3[3 * m], s3[3 * m + 1], s3[3 * m + 2], s2[2 * m], s2[2 * m + 1], th2);
+        cnt += in ? 1 : 0;
+        if (mask) mask[m] = in ? 1 : 0;
+    }
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    int tot = 0;
+#pragma unroll
+    for (int wv = 0; wv < SCENE_WAVES; ++wv) tot += red[wv];
+    return tot;
 }
 
 // ---- Philox4x32-10, the generator of every sampler (cvxs::sample_sets_kernel, sample_scenes_kernel, cvxnl::sample_assemble_kernel)

@@ -15,9 +15,8 @@
 
 namespace cvxn {
 
-constexpr int SCENE_BLOCK = 256;  // lanes of the sampling / scoring / selection / refit workgroups
+// (SCENE_BLOCK, the lanes of every workgroup here, SCENE_WAVES and block_inliers: ransac_common.h)
 constexpr int SCENE_TILE = 512;   // correspondences per LDS tile of the scoring kernel (20 KB)
-constexpr int SCENE_WAVES = SCENE_BLOCK / 64;
 
 // ---- sampling: one lane per (scene, hypothesis), grid (ceil(H / 256), scenes).  The draw of cvxs::sample_sets_kernel for k = 4 over the
 // scene's own M_f, with the scene's own seed as the Philox key and the hypothesis index WITHIN the scene as the counter: scene f draws
@@ -115,25 +114,6 @@ __global__ void __launch_bounds__(SCENE_BLOCK) score_scenes_kernel(ScoreScenesAr
             cnt += usable && is_inlier(cam, scene[i * 5], scene[i * 5 + 1], scene[i * 5 + 2], scene[i * 5 + 3], scene[i * 5 + 4], th2) ? 1 : 0;
     }
     if (live) a.count[g] = cnt;
-}
-
-// inliers of ONE pose over one scene, by the lanes of one workgroup: writes mask (optional) and returns the count to every lane
-__device__ inline int block_inliers(const Camera &cam, int n, const double *s2, const double *s3, double th2, uint8_t *mask, int *red /* LDS, SCENE_WAVES ints */)
-{
-    int cnt = 0;
-    for (int m = threadIdx.x; m < n; m += SCENE_BLOCK) {
-        const bool in = is_inlier(cam, s3[3 * m], s3[3 * m + 1], s3[3 * m + 2], s2[2 * m], s2[2 * m + 1], th2);
-        cnt += in ? 1 : 0;
-        if (mask) mask[m] = in ? 1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_down(cnt, o);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = cnt;
-    __syncthreads();
-    int tot = 0;
-#pragma unroll
-    for (int wv = 0; wv < SCENE_WAVES; ++wv) tot += red[wv];
-    return tot;
 }
 
 // ---- selection: ONE workgroup per scene.  Arg-max of the scene's H counts with the LOWEST index winning a tie, the number of certified

@@ -303,6 +303,195 @@ def refit_update_scenes(sc: Scenes, fit, fit_count, thresh, R, t, head, mask):
           sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask))
 
 
+# ---- a hypothesis budget per scene, solved in rounds (include/cvxpnpl_amd_ransac_adaptive.h) ----------------------
+# ransac_pnp_batch(confidence=...) stops a scene once the standard rule says that, at the inlier share its best hypothesis shows, enough
+# minimal sets have been drawn.  Round r draws round_hyp further hypotheses for the scenes still ACTIVE; their minimal problems are compact
+# (entry a of the active list, hypothesis h of the round: problem a * n_round + h), what lasts over the rounds is indexed by the scene.
+# The kernels are those of libcvxpnpl_amd_ransac_adaptive.so; the stage wrappers below check every tensor as _chk does.
+
+
+class AdaptiveState:
+    """What an adaptive call keeps over its rounds, on the scenes' device: active, active_next [F] int32 (the first n entries count),
+    n_active [1] int32, done [F] int32, R [F,3,3], t [F,3], head [F,4] int32, best [F] int32 (the count of the running winner), mask
+    [total] uint8, hyp_used [F] int32.  Built by adaptive_init."""
+
+    def __init__(self, F, total, dev):
+        i32 = dict(dtype=torch.int32, device=dev)
+        self.active, self.active_next, self.done = torch.empty((F,), **i32), torch.empty((F,), **i32), torch.empty((F,), **i32)
+        self.n_active, self.head, self.best, self.hyp_used = torch.empty((1,), **i32), torch.empty((F, 4), **i32), torch.empty((F,), **i32), torch.empty((F,), **i32)
+        self.R = torch.empty((F, 3, 3), dtype=torch.float64, device=dev)
+        self.t = torch.empty((F, 3), dtype=torch.float64, device=dev)
+        self.mask = torch.empty((total,), dtype=torch.uint8, device=dev)
+
+    def swap(self):
+        """After compact_active: the compacted list becomes the active one."""
+        self.active, self.active_next = self.active_next, self.active
+
+
+def needed_hypotheses(inliers: int, n_corr: int, confidence: float) -> float:
+    """cvxpnpl_ransac_adaptive_needed_host: N = log(1 - confidence) / log1p(-q), q = prod_{j<4} (inliers - j) / (n_corr - j), by the function
+    the update kernel calls.  inf for inliers < 4, 0 for inliers >= n_corr.  No GPU needed."""
+    return float(_lib.ransac_adaptive_lib().cvxpnpl_ransac_adaptive_needed_host(int(inliers), int(n_corr), float(confidence)))
+
+
+def _check_adaptive(confidence, round_hyp):
+    """Host-side validation of the adaptive keywords (nothing here needs a GPU)."""
+    c = float(confidence)
+    if not (0.0 < c < 1.0):  # (NaN and the infinities compare false)
+        raise ValueError(f"confidence must lie inside (0, 1), got {confidence!r}")
+    if int(round_hyp) < 1:
+        raise ValueError(f"round_hyp must be at least 1, got {round_hyp!r}")
+    return c, int(round_hyp)
+
+
+def _call_adaptive(sc: Scenes, name, *args):
+    with torch.cuda.device(sc.device):
+        L = _lib.ransac_adaptive_lib()
+        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_adaptive_last_error().decode()}")
+
+
+def _chk_active(sc: Scenes, active, n_active):
+    """active: int32 on the scenes' device, one dimension, at least n_active entries (the kernels read the first n_active)."""
+    A = int(n_active)
+    if A < 0:
+        raise ValueError("n_active must not be negative")
+    if not isinstance(active, torch.Tensor) or active.dim() != 1 or active.shape[0] < A:
+        raise ValueError(f"active must be a tensor of at least n_active = {A} entries")
+    _chk(active, "active", torch.int32, (active.shape[0],), sc.device)
+    return A
+
+
+def _chk_budget(hyp0, n_round, cap):
+    h0, Hr, cp = int(hyp0), int(n_round), int(cap)
+    if h0 < 0 or Hr < 0 or cp < 0 or h0 + Hr > cp:
+        raise ValueError(f"a round needs 0 <= hyp0, 0 <= n_round and hyp0 + n_round <= cap, got {h0}, {Hr}, {cp}")
+    return h0, Hr, cp
+
+
+def _chk_state(sc: Scenes, st: AdaptiveState):
+    dev, i32 = sc.device, torch.int32
+    for name, shape, dt in (("active", (sc.F,), i32), ("active_next", (sc.F,), i32), ("done", (sc.F,), i32), ("n_active", (1,), i32),
+                            ("head", (sc.F, 4), i32), ("best", (sc.F,), i32), ("hyp_used", (sc.F,), i32), ("R", (sc.F, 3, 3), torch.float64),
+                            ("t", (sc.F, 3), torch.float64), ("mask", (sc.total,), torch.uint8)):
+        _chk(getattr(st, name), "state." + name, dt, shape, dev)
+    if st.active.data_ptr() == st.active_next.data_ptr():
+        raise ValueError("state.active and state.active_next are the same buffer")
+
+
+def adaptive_init(sc: Scenes) -> AdaptiveState:
+    """cvxpnpl_ransac_adaptive_init: the state of a call, every scene active, nothing drawn (head[f] = (3, -1, 0, 0), best[f] = -1)."""
+    _require_gpu()
+    _chk_scenes(sc)
+    st = AdaptiveState(sc.F, sc.total, sc.device)
+    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_init", sc.F, _ptr(st.active), _ptr(st.n_active), _ptr(st.head), _ptr(st.best), _ptr(st.hyp_used))
+    return st
+
+
+def sample_active(sc: Scenes, active, n_active: int, hyp0: int, n_round: int, cap: int, seeds=None, want_idx: bool = False):
+    """cvxpnpl_ransac_adaptive_sample: for entry a < n_active of `active`, the hypotheses hyp0 .. hyp0 + n_round - 1 of scene active[a] --
+    the rows [f, hyp0 : hyp0 + n_round] of sample_scenes(sc, hyp0 + n_round).  Returns (p2 [A*n_round,4,2], p3 [A*n_round,4,3], K_hyp
+    [A*n_round,3,3] or None) and, with want_idx, idx [A*n_round,4] int32.  An entry outside [0, F) leaves its rows unwritten."""
+    _require_gpu()
+    _chk_scenes(sc)
+    A, dev = _chk_active(sc, active, n_active), sc.device
+    h0, Hr, cp = _chk_budget(hyp0, n_round, cap)
+    if seeds is None:
+        if sc.seeds is None:
+            raise ValueError("no seeds: give them here or to pack_scenes")
+        sd = sc.seeds
+    else:
+        if len(seeds) != sc.F:
+            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
+        sd = torch.as_tensor(_seed_words(seeds)).to(dev)
+    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
+    n = A * Hr
+    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
+    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
+    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
+    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
+    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_sample", sc.F, A, _ptr(active), h0, Hr, cp, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(sc.x), _ptr(sc.X),
+                   _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
+
+
+def _chk_round(sc, A, R, t, status, count=None):
+    """The poses of a round: R [A*n_round,3,3] with n_round >= 1, and t, status, count of that length.  Returns n_round."""
+    if A < 1:
+        return 0
+    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % A or R.shape[0] < A:
+        raise ValueError("R must be [n_active*n_round,3,3] with n_round >= 1")
+    n = R.shape[0]
+    _chk(R, "R", torch.float64, (n, 3, 3), sc.device)
+    _chk(t, "t", torch.float64, (n, 3), sc.device)
+    if status is not None:
+        _chk(status, "status", torch.int32, (n,), sc.device)
+    if count is not None:
+        _chk(count, "count", torch.int32, (n,), sc.device)
+    return n // A
+
+
+def score_active(sc: Scenes, active, n_active: int, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
+    """cvxpnpl_ransac_adaptive_score: count [A*n_round] int32, the inliers of (R, t)[a*n_round + h] among the correspondences of scene
+    active[a]; predicate and status rule of score_scenes."""
+    _require_gpu()
+    _chk_scenes(sc)
+    A = _chk_active(sc, active, n_active)
+    Hr = _chk_round(sc, A, R, t, status)
+    count = torch.empty((A * Hr,), dtype=torch.int32, device=sc.device)
+    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_score", sc.F, A, _ptr(active), Hr, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status),
+                   _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(count))
+    return count
+
+
+def update_active(sc: Scenes, st: AdaptiveState, n_active: int, hyp0: int, cap: int, confidence: float, count, R, t, status, thresh: float = 2.0):
+    """cvxpnpl_ransac_adaptive_update on the first n_active entries of st.active: the round's best replaces a scene's running best only
+    by a strictly higher count (pose, head, best and mask together), certified hypotheses accumulate, hyp_used[f] = hyp0 + n_round, and
+    st.done[a] says whether the scene is finished.  n_round is R.shape[0] / n_active.  In place, no synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk_state(sc, st)
+    conf, _ = _check_adaptive(confidence, 1)
+    A = _chk_active(sc, st.active, n_active)
+    if status is None:
+        raise ValueError("status is required")
+    Hr = _chk_round(sc, A, R, t, status, count)
+    h0, Hr, cp = _chk_budget(hyp0, Hr, cap)
+    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, _ptr(sc.offsets), sc.total, _ptr(count), _ptr(R),
+                   _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+                   _ptr(st.best), _ptr(st.mask), _ptr(st.hyp_used), _ptr(st.done))
+
+
+def compact_active(sc: Scenes, st: AdaptiveState, n_active: int):
+    """cvxpnpl_ransac_adaptive_compact: st.active_next = the entries a < n_active of st.active with st.done[a] == 0, in order, and
+    st.n_active[0] their number.  No synchronisation; the caller reads st.n_active back and calls st.swap()."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk_state(sc, st)
+    A = _chk_active(sc, st.active, n_active)
+    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_compact", sc.F, A, _ptr(st.active), _ptr(st.done), _ptr(st.active_next), _ptr(st.n_active))
+
+
+def _adaptive_rounds(sc, cap, conf, round_hyp, thresh, eps, max_iters, solver_opts):
+    """The rounds of ransac_pnp_batch(confidence=...): returns the state and the number of rounds.  One 4-byte read-back per round -- the
+    number of scenes still active, which the next round's solve needs as a host number (its batch size)."""
+    st = adaptive_init(sc)
+    A, h0, rounds = sc.F, 0, 0
+    while A > 0 and h0 < cap:
+        Hr = min(round_hyp, cap - h0)
+        p2, p3, Kh = sample_active(sc, st.active, A, h0, Hr, cap)
+        res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+        count = score_active(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+        update_active(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
+        compact_active(sc, st, A)
+        A = int(st.n_active.cpu()[0])   # the round's one synchronisation
+        st.swap()
+        h0 += Hr
+        rounds += 1
+    return st, rounds
+
+
 class _Fit:
     """What refit_update_*_scenes reads of a refit: R, t, status."""
 
@@ -328,7 +517,8 @@ def _polish(sc, R, t, head, mask_pts, mask_lines, thresh):
 
 
 def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
-                     refit_rounds: int = 1, sizes=None, device=None, polish: bool = False, **solver_opts):
+                     refit_rounds: int = 1, sizes=None, device=None, polish: bool = False, confidence: Optional[float] = None, round_hyp: int = 64,
+                     **solver_opts):
     """Robust PnP for F scenes of different sizes in one launch sequence (what ransac_pnp does for one scene per call).
 
     Scenes: lists of F arrays pts_2d[f] [M_f,2] / pts_3d[f] [M_f,3], or packed [sum M,2] / [sum M,3] with `sizes` (a host sequence of F
@@ -338,9 +528,17 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     inliers[offsets[f]:offsets[f+1]]) on the device; n_inliers, status, n_certified, best_index [F] (host, columns of the one read-back
     `head` [F,4], each row what select_best's head is for one scene); sizes, n_hyp.  One host synchronisation per call.
     polish=True: after the refits the pose is refined on the pixel reprojection error of its consensus set (refine.refine_scenes) and kept
-    when it holds at least that consensus; the result gains "refine": device tensors cost [F,2], iters, status [F]."""
+    when it holds at least that consensus; the result gains "refine": device tensors cost [F,2], iters, status [F].
+    confidence (0 < confidence < 1; None: the fixed budget above, unchanged): n_hyp becomes the CAP per scene and the hypotheses are drawn
+    and solved in rounds of round_hyp.  Scene f stops once it has drawn N = log(1 - confidence) / log1p(-q) hypotheses, q the chance that
+    a minimal set is all inliers at the scene's best inlier count so far, or n_hyp.  A scene that stops after u hypotheses holds what the
+    fixed budget n_hyp = u selects (same draws, lowest index on a tie); refits and polish then run over all scenes as above.  The result
+    gains hyp_used [F] (host int32), rounds and confidence.  One 4-byte read-back per round on top of the call's own: the number of scenes
+    still active is the next solve's batch size, a host number."""
     szs = _check_scenes(pts_2d, pts_3d, K, sizes)
     F = len(szs)
+    if confidence is not None:
+        conf, round_hyp = _check_adaptive(confidence, round_hyp)
     if seed is None:
         seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
     if isinstance(seed, (int, _np.integer)):
@@ -352,11 +550,15 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     if int(n_hyp) < 1:
         raise ValueError("n_hyp must be at least 1")
     sc = pack_scenes(pts_2d, pts_3d, K, sizes=szs if sizes is not None else None, device=device, seeds=seeds)
-    p2, p3, Kh = sample_scenes(sc, n_hyp)
-    # no torch kernel from here to the read-back: the F * n_hyp minimal solves in one launch sequence of the solver library ...
-    res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
-    count = score_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
-    R, t, head, mask = select_scenes(sc, count, res.R, res.t, res.status, thresh)
+    if confidence is not None:
+        state, rounds = _adaptive_rounds(sc, int(n_hyp), conf, round_hyp, thresh, eps, max_iters, solver_opts)
+        R, t, head, mask = state.R, state.t, state.head, state.mask
+    else:
+        p2, p3, Kh = sample_scenes(sc, n_hyp)
+        # no torch kernel from here to the read-back: the F * n_hyp minimal solves in one launch sequence of the solver library ...
+        res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+        count = score_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+        R, t, head, mask = select_scenes(sc, count, res.R, res.t, res.status, thresh)
     if refit:
         for _ in range(max(1, int(refit_rounds))):  # ... and the F refits of the consensus sets in one solve at the cost seam
             Bt, Qt, cnt = assemble_consensus(sc, mask)
@@ -368,6 +570,8 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
            "best_index": h[:, 2], "head": h, "sizes": sc.sizes, "n_hyp": int(n_hyp)}
     if polish:
         out["refine"] = refined
+    if confidence is not None:
+        out.update(hyp_used=state.hyp_used.cpu(), rounds=rounds, confidence=conf)
     return out
 
 
