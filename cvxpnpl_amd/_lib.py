@@ -396,6 +396,36 @@ def ransac_adaptive_lib():
     return L
 
 
+# guided RANSAC, minimal sets drawn from the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h): the tenth library
+RANSAC_GUIDED_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_guided.so")
+RANSAC_GUIDED_EXPORTS = ("cvxpnpl_ransac_guided_rank", "cvxpnpl_ransac_guided_sample", "cvxpnpl_ransac_guided_sample_active",
+                         "cvxpnpl_ransac_guided_rank_host", "cvxpnpl_ransac_guided_pool_host", "cvxpnpl_ransac_guided_last_error")
+
+_ransac_guided_lib = None
+
+
+def ransac_guided_lib():
+    """Load libcvxpnpl_amd_ransac_guided.so (loudly)."""
+    global _ransac_guided_lib
+    if _ransac_guided_lib is not None:
+        return _ransac_guided_lib
+    if not os.path.exists(RANSAC_GUIDED_LIB_PATH):
+        raise LibraryMissing(f"{RANSAC_GUIDED_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(RANSAC_GUIDED_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    L.cvxpnpl_ransac_guided_rank.argtypes = [i64, p, i64, i32, p, p, p]
+    L.cvxpnpl_ransac_guided_sample.argtypes = [i64, i32, i32, p, i64, p, p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_guided_sample_active.argtypes = [i64, i64, p, i32, i32, i32, i32, p, i64, p, p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_guided_rank_host.argtypes = [i64, p, i64, p, p, i32]
+    for name in RANSAC_GUIDED_EXPORTS[:4]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_ransac_guided_pool_host.argtypes = [i32, i32, i32]
+    L.cvxpnpl_ransac_guided_pool_host.restype = i32
+    L.cvxpnpl_ransac_guided_last_error.restype = C.c_char_p
+    _ransac_guided_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

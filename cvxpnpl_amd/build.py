@@ -149,6 +149,19 @@ def ransac_adaptive_compile_cmd(out=RANSAC_ADAPTIVE_OUT):
     return ransac_compile_cmd(out)[:-1] + [RANSAC_ADAPTIVE_SRC]
 
 
+# guided RANSAC, minimal sets drawn from the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h): the tenth library, the
+# flags of the third
+RANSAC_GUIDED_SRC = os.path.join(HERE, "csrc", "ransac_guided_hip.hip")
+RANSAC_GUIDED_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_guided.so")
+RANSAC_GUIDED_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_guided.resources.txt")
+RANSAC_GUIDED_DEPS = [RANSAC_GUIDED_SRC, os.path.join(HERE, "csrc", "ransac_guided_kernel.h"), os.path.join(HERE, "csrc", "ransac_guided_core.h"),
+                      os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_guided.h")]
+
+
+def ransac_guided_compile_cmd(out=RANSAC_GUIDED_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_GUIDED_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -199,8 +212,12 @@ def build_ransac_adaptive(force=False, verbose=False):
     return _build_one(RANSAC_ADAPTIVE_OUT, RANSAC_ADAPTIVE_RESOURCES, RANSAC_ADAPTIVE_DEPS, ransac_adaptive_compile_cmd(), force, verbose)
 
 
+def build_ransac_guided(force=False, verbose=False):
+    return _build_one(RANSAC_GUIDED_OUT, RANSAC_GUIDED_RESOURCES, RANSAC_GUIDED_DEPS, ransac_guided_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All nine libraries; returns the solver's (OUT)."""
+    """All ten libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -210,6 +227,7 @@ def build(force=False, verbose=False):
     build_refine_robust(force, verbose)
     build_refine_robust_grad(force, verbose)
     build_ransac_adaptive(force, verbose)
+    build_ransac_guided(force, verbose)
     return OUT
 
 

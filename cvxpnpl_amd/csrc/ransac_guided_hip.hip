@@ -1,0 +1,193 @@
+// ransac_guided_hip.hip -- entry points of guided RANSAC over many scenes (include/cvxpnpl_amd_ransac_guided.h), built as
+// libcvxpnpl_amd_ransac_guided.so.  The kernels are ransac_guided_kernel.h, the pool rule and the ranking order ransac_guided_core.h.
+// Every entry point checks its arguments before it launches anything.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stdio.h>
+
+#include <algorithm>
+#include <thread>
+#include <vector>
+
+#include "../../include/cvxpnpl_amd_ransac_guided.h"
+#include "ransac_guided_kernel.h"
+
+namespace {
+
+thread_local char g_err[512] = "";
+
+int set_err(const char *what, hipError_t e)
+{
+    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
+    return -2;
+}
+
+int bad(const char *who, const char *what)
+{
+    snprintf(g_err, sizeof(g_err), "%s: bad arguments (%s)", who, what);
+    return -1;
+}
+
+// what the two samplers share: the sizes, checked before a zero-size call returns ...
+const char *check_sizes(int64_t n_scenes, int64_t n_total, int32_t pool_full)
+{
+    if (n_scenes < 0) return "negative n_scenes";
+    if (n_total < 0) return "negative n_total";
+    if (n_scenes > 0x7fffffffLL) return "more scenes than an int32 index holds";
+    if (pool_full < 0) return "negative pool_full";
+    return nullptr;
+}
+
+// ... and the pointers of a call that launches: the offsets, the packed scene, the ranking, the outputs.  Returns a message or null.
+const char *check_draw(const int64_t *off, int64_t n_total, const double *s2, const double *s3, int32_t pool_full, const uint64_t *seeds,
+                       const int32_t *order, const double *K, const double *p2, const double *p3, const double *Kh)
+{
+    if (!off) return "d_offsets is null";
+    if (n_total > 0 && (!s2 || !s3)) return "d_scene_2d or d_scene_3d is null";
+    if (!seeds) return "d_seeds is null";
+    if (pool_full > 0 && !order) return "d_order is null";
+    if (!p2 || !p3) return "d_pts_2d or d_pts_3d is null";
+    if ((K == nullptr) != (Kh == nullptr)) return "d_K and d_K_hyp go together";
+    return nullptr;
+}
+
+constexpr int64_t GRID_Y = 65535; // scenes (or active entries) per launch of a kernel whose grid is (x, scenes)
+
+int launched(const char *what)
+{
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? 0 : set_err(what, e);
+}
+
+// the clamped slice of a scene on the host: cvxn::scene_slice
+void host_slice(const int64_t *off, int64_t f, int64_t n_total, int64_t &beg, int64_t &n)
+{
+    int64_t e = off[f + 1], b = off[f];
+    e = e < 0 ? 0 : (e > n_total ? n_total : e);
+    b = b < 0 ? 0 : (b > e ? e : b);
+    n = e - b > 0x7fffffffLL ? 0x7fffffffLL : e - b;
+    beg = b;
+}
+
+} // namespace
+
+extern "C" const char *cvxpnpl_ransac_guided_last_error(void) { return g_err; }
+
+extern "C" int32_t cvxpnpl_ransac_guided_pool_host(int32_t h, int32_t n_corr, int32_t pool_full)
+{
+    if (h < 0 || n_corr < cvxng::MINIMAL || pool_full < 0) return -1;
+    return cvxng::pool_size(h, n_corr, pool_full);
+}
+
+extern "C" int cvxpnpl_ransac_guided_rank_host(int64_t n_scenes, const int64_t *offsets, int64_t n_total, const double *quality, int32_t *order,
+                                               int32_t n_threads)
+{
+    const char *who = "cvxpnpl_ransac_guided_rank_host";
+    if (n_scenes < 0) return bad(who, "negative n_scenes");
+    if (n_total < 0) return bad(who, "negative n_total");
+    if (n_scenes == 0 || n_total == 0) return 0;
+    if (!offsets) return bad(who, "offsets is null");
+    if (!quality) return bad(who, "quality is null");
+    if (!order) return bad(who, "order is null");
+    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
+    if (nt < 1) nt = 1;
+    if ((int64_t)nt > n_scenes) nt = (int)n_scenes;
+    auto work = [&](int64_t lo, int64_t hi) {
+        for (int64_t f = lo; f < hi; ++f) {
+            int64_t beg, n;
+            host_slice(offsets, f, n_total, beg, n);
+            const double *q = quality + beg;
+            for (int64_t m = 0; m < n; ++m) { // the kernel's lane m
+                const double key = cvxng::quality_key(q[m]);
+                int64_t rank = 0;
+                for (int64_t j = 0; j < n; ++j) rank += cvxng::ranks_before(cvxng::quality_key(q[j]), (int32_t)j, key, (int32_t)m) ? 1 : 0;
+                order[beg + rank] = (int32_t)m;
+            }
+        }
+    };
+    if (nt == 1) { work(0, n_scenes); return 0; }
+    std::vector<std::thread> pool;
+    const int64_t chunk = (n_scenes + nt - 1) / nt;
+    for (int k = 0; k < nt; ++k) {
+        const int64_t lo = k * chunk, hi = std::min<int64_t>(n_scenes, lo + chunk);
+        if (lo < hi) pool.emplace_back(work, lo, hi);
+    }
+    for (auto &th : pool) th.join();
+    return 0;
+}
+
+extern "C" int cvxpnpl_ransac_guided_rank(int64_t n_scenes, const int64_t *d_offsets, int64_t n_total, int32_t max_corr, const double *d_quality,
+                                          int32_t *d_order, void *stream)
+{
+    const char *who = "cvxpnpl_ransac_guided_rank";
+    if (n_scenes < 0) return bad(who, "negative n_scenes");
+    if (n_total < 0) return bad(who, "negative n_total");
+    if (max_corr < 0) return bad(who, "negative max_corr");
+    if (n_scenes > 0x7fffffffLL) return bad(who, "more scenes than an int32 index holds");
+    if (n_scenes == 0 || n_total == 0 || max_corr == 0) return 0;
+    if (!d_offsets) return bad(who, "d_offsets is null");
+    if (!d_quality) return bad(who, "d_quality is null");
+    if (!d_order) return bad(who, "d_order is null");
+    cvxng::RankArgs a;
+    a.n_scenes = n_scenes; a.n_total = n_total; a.off = d_offsets; a.quality = d_quality; a.order = d_order;
+    const unsigned gx = (unsigned)(((int64_t)max_corr + cvxng::SCENE_BLOCK - 1) / cvxng::SCENE_BLOCK);
+    for (int64_t f0 = 0; f0 < n_scenes; f0 += GRID_Y) {
+        a.scene0 = f0;
+        const int64_t ny = n_scenes - f0 < GRID_Y ? n_scenes - f0 : GRID_Y;
+        hipLaunchKernelGGL(cvxng::rank_quality_kernel, dim3(gx, (unsigned)ny), dim3(cvxng::SCENE_BLOCK), 0, (hipStream_t)stream, a);
+    }
+    return launched("rank_quality_kernel launch");
+}
+
+extern "C" int cvxpnpl_ransac_guided_sample(int64_t n_scenes, int32_t n_hyp, int32_t pool_full, const int64_t *d_offsets, int64_t n_total,
+                                            const uint64_t *d_seeds, const int32_t *d_order, const double *d_scene_2d, const double *d_scene_3d,
+                                            const double *d_K, int32_t *d_idx, double *d_pts_2d, double *d_pts_3d, double *d_K_hyp, void *stream)
+{
+    const char *who = "cvxpnpl_ransac_guided_sample";
+    if (const char *m = check_sizes(n_scenes, n_total, pool_full)) return bad(who, m);
+    if (n_hyp < 0) return bad(who, "negative n_hyp");
+    if (n_scenes == 0 || n_hyp == 0) return 0;
+    if (const char *m = check_draw(d_offsets, n_total, d_scene_2d, d_scene_3d, pool_full, d_seeds, d_order, d_K, d_pts_2d, d_pts_3d, d_K_hyp))
+        return bad(who, m);
+    cvxng::SampleGuidedArgs a;
+    a.n_scenes = n_scenes; a.n_total = n_total; a.n_hyp = n_hyp; a.pool_full = pool_full; a.off = d_offsets; a.seed = d_seeds; a.order = d_order;
+    a.s2 = d_scene_2d; a.s3 = d_scene_3d; a.K = d_K; a.idx = d_idx; a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.Kh = d_K_hyp;
+    const unsigned gx = (unsigned)(((int64_t)n_hyp + cvxng::SCENE_BLOCK - 1) / cvxng::SCENE_BLOCK);
+    for (int64_t f0 = 0; f0 < n_scenes; f0 += GRID_Y) {
+        a.scene0 = f0;
+        const int64_t ny = n_scenes - f0 < GRID_Y ? n_scenes - f0 : GRID_Y;
+        hipLaunchKernelGGL(cvxng::sample_guided_kernel, dim3(gx, (unsigned)ny), dim3(cvxng::SCENE_BLOCK), 0, (hipStream_t)stream, a);
+    }
+    return launched("sample_guided_kernel launch");
+}
+
+extern "C" int cvxpnpl_ransac_guided_sample_active(int64_t n_scenes, int64_t n_active, const int32_t *d_active, int32_t hyp0, int32_t n_round,
+                                                   int32_t cap, int32_t pool_full, const int64_t *d_offsets, int64_t n_total,
+                                                   const uint64_t *d_seeds, const int32_t *d_order, const double *d_scene_2d,
+                                                   const double *d_scene_3d, const double *d_K, int32_t *d_idx, double *d_pts_2d,
+                                                   double *d_pts_3d, double *d_K_hyp, void *stream)
+{
+    const char *who = "cvxpnpl_ransac_guided_sample_active";
+    if (n_active < 0) return bad(who, "negative n_active");
+    if (n_active > 0x7fffffffLL) return bad(who, "more active scenes than an int32 index holds");
+    if (const char *m = check_sizes(n_scenes, n_total, pool_full)) return bad(who, m);
+    if (hyp0 < 0) return bad(who, "negative hyp0");
+    if (n_round < 0) return bad(who, "negative n_round");
+    if (cap < 0) return bad(who, "negative cap");
+    if ((int64_t)hyp0 + n_round > (int64_t)cap) return bad(who, "hyp0 + n_round exceeds cap");
+    if (n_scenes == 0 || n_active == 0 || n_round == 0) return 0;
+    if (!d_active) return bad(who, "d_active is null");
+    if (const char *m = check_draw(d_offsets, n_total, d_scene_2d, d_scene_3d, pool_full, d_seeds, d_order, d_K, d_pts_2d, d_pts_3d, d_K_hyp))
+        return bad(who, m);
+    cvxng::SampleGuidedActiveArgs a;
+    a.n_active = n_active; a.n_scenes = n_scenes; a.n_total = n_total; a.hyp0 = hyp0; a.n_round = n_round; a.pool_full = pool_full;
+    a.active = d_active; a.off = d_offsets; a.seed = d_seeds; a.order = d_order; a.s2 = d_scene_2d; a.s3 = d_scene_3d; a.K = d_K; a.idx = d_idx;
+    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.Kh = d_K_hyp;
+    const unsigned gx = (unsigned)(((int64_t)n_round + cvxng::SCENE_BLOCK - 1) / cvxng::SCENE_BLOCK);
+    for (int64_t a0 = 0; a0 < n_active; a0 += GRID_Y) {
+        a.act0 = a0;
+        const int64_t ny = n_active - a0 < GRID_Y ? n_active - a0 : GRID_Y;
+        hipLaunchKernelGGL(cvxng::sample_guided_active_kernel, dim3(gx, (unsigned)ny), dim3(cvxng::SCENE_BLOCK), 0, (hipStream_t)stream, a);
+    }
+    return launched("sample_guided_active_kernel launch");
+}

@@ -473,14 +473,139 @@ def compact_active(sc: Scenes, st: AdaptiveState, n_active: int):
     _call_adaptive(sc, "cvxpnpl_ransac_adaptive_compact", sc.F, A, _ptr(st.active), _ptr(st.done), _ptr(st.active_next), _ptr(st.n_active))
 
 
-def _adaptive_rounds(sc, cap, conf, round_hyp, thresh, eps, max_iters, solver_opts):
+# ---- guided sampling: the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h) ----------------
+# ransac_pnp_batch(quality=...) ranks every scene's correspondences by a matcher's score once per call and draws hypothesis h from the
+# n(h) best of them; the pool grows with h (the growth function of PROSAC) and is the whole scene from h = pool_full on, where the draw is
+# the uniform one again.  The kernels are those of libcvxpnpl_amd_ransac_guided.so; the stage wrappers below check every tensor as _chk does.
+
+
+def _call_guided(sc: Scenes, name, *args):
+    with torch.cuda.device(sc.device):
+        L = _lib.ransac_guided_lib()
+        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_guided_last_error().decode()}")
+
+
+def _chk_pool_full(pool_full):
+    if isinstance(pool_full, bool) or not isinstance(pool_full, (int, _np.integer)) or not 0 <= int(pool_full) <= 0x7FFFFFFF:
+        raise ValueError(f"pool_full must be an int >= 0 (and below 2^31), got {pool_full!r}")
+    return int(pool_full)
+
+
+def pool_size(h: int, n_corr: int, pool_full: int) -> int:
+    """cvxpnpl_ransac_guided_pool_host: the number of best-ranked correspondences that hypothesis h of a scene of n_corr draws from, by the
+    function the sampling kernels call.  n_corr from h = pool_full on; before, min(n_T(h), 4 + h, n_corr) with n_T(h) the smallest n whose
+    share pool_full * C(n,4) / C(n_corr,4) of the uniform draws reaches h + 1.  No GPU needed."""
+    h, m, pf = int(h), int(n_corr), _chk_pool_full(pool_full)
+    if not 0 <= h <= 0x7FFFFFFF or not 4 <= m <= 0x7FFFFFFF:
+        raise ValueError(f"pool_size needs 0 <= h and 4 <= n_corr (both below 2^31), got {h}, {m}")
+    return int(_lib.ransac_guided_lib().cvxpnpl_ransac_guided_pool_host(h, m, pf))
+
+
+def _seeds_dev(sc: Scenes, seeds):
+    if seeds is None:
+        if sc.seeds is None:
+            raise ValueError("no seeds: give them here or to pack_scenes")
+        sd = sc.seeds
+    else:
+        if len(seeds) != sc.F:
+            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
+        sd = torch.as_tensor(_seed_words(seeds)).to(sc.device)
+    return _chk(sd, "seeds", torch.int64, (sc.F,), sc.device)
+
+
+def rank_scenes(sc: Scenes, quality):
+    """cvxpnpl_ransac_guided_rank: order [total] int32 from quality [total] float64 (higher is better) on the scenes' device.  Scene f's
+    slice of order is a permutation of 0 .. M_f - 1, best first: j before m when its quality is greater, or equal with j < m; a NaN counts
+    as -inf.  A counting rank, O(M_f^2) per scene.  No synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk(quality, "quality", torch.float64, (sc.total,), sc.device)
+    order = torch.empty((sc.total,), dtype=torch.int32, device=sc.device)
+    _call_guided(sc, "cvxpnpl_ransac_guided_rank", sc.F, _ptr(sc.offsets), sc.total, max(sc.sizes), _ptr(quality), _ptr(order))
+    return order
+
+
+def sample_scenes_guided(sc: Scenes, n_hyp: int, order, pool_full: int, seeds=None, want_idx: bool = False):
+    """cvxpnpl_ransac_guided_sample: what sample_scenes returns, hypothesis h of scene f drawn from the pool_size(h, M_f, pool_full) best
+    entries of the scene's slice of order (rank_scenes).  pool_full = 0 is sample_scenes bit for bit.  An order entry outside [0, M_f)
+    gives the NaN hypothesis with idx = -1."""
+    _require_gpu()
+    _chk_scenes(sc)
+    H, dev, pf = int(n_hyp), sc.device, _chk_pool_full(pool_full)
+    if H < 0:
+        raise ValueError("n_hyp must not be negative")
+    _chk(order, "order", torch.int32, (sc.total,), dev)
+    sd = _seeds_dev(sc, seeds)
+    n = sc.F * H
+    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
+    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
+    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
+    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
+    _call_guided(sc, "cvxpnpl_ransac_guided_sample", sc.F, H, pf, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(order), _ptr(sc.x), _ptr(sc.X),
+                 _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
+
+
+def sample_active_guided(sc: Scenes, active, n_active: int, hyp0: int, n_round: int, cap: int, order, pool_full: int, seeds=None,
+                         want_idx: bool = False):
+    """cvxpnpl_ransac_guided_sample_active: what sample_active returns, drawn as sample_scenes_guided draws -- the rows
+    [f, hyp0 : hyp0 + n_round] of sample_scenes_guided(sc, hyp0 + n_round, order, pool_full) for f = active[a].  An entry of active outside
+    [0, F) leaves its rows unwritten."""
+    _require_gpu()
+    _chk_scenes(sc)
+    A, dev, pf = _chk_active(sc, active, n_active), sc.device, _chk_pool_full(pool_full)
+    h0, Hr, cp = _chk_budget(hyp0, n_round, cap)
+    _chk(order, "order", torch.int32, (sc.total,), dev)
+    sd = _seeds_dev(sc, seeds)
+    n = A * Hr
+    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
+    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
+    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
+    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
+    _call_guided(sc, "cvxpnpl_ransac_guided_sample_active", sc.F, A, _ptr(active), h0, Hr, cp, pf, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(order),
+                 _ptr(sc.x), _ptr(sc.X), _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
+
+
+def _check_quality(quality, pool_full, szs, packed, n_hyp):
+    """Host-side validation of the guided keywords (nothing here needs a GPU): returns pool_full (None without quality; n_hyp by default)."""
+    if quality is None:
+        if pool_full is not None:
+            raise ValueError("pool_full given without quality")
+        return None
+    if packed:
+        sq = _shape(quality)
+        if len(sq) != 1 or sq[0] != sum(szs):
+            raise ValueError(f"quality: expected [{sum(szs)}] for the packed scenes, got {sq}")
+    else:
+        if not isinstance(quality, (list, tuple)):
+            raise ValueError("quality is a list of F arrays [M_f], or packed [sum M] with `sizes`")
+        if len(quality) != len(szs):
+            raise ValueError(f"quality for {len(quality)} scenes, {len(szs)} scenes given")
+        for f, q in enumerate(quality):
+            if _shape(q) != (szs[f],):
+                raise ValueError(f"scene {f}: quality {_shape(q)}, expected [{szs[f]}]")
+    for q in (quality if isinstance(quality, (list, tuple)) else (quality,)):
+        dt = q.dtype if hasattr(q, "dtype") else _np.asarray(q).dtype
+        if (isinstance(dt, torch.dtype) and (dt.is_complex or dt == torch.bool)) or (not isinstance(dt, torch.dtype) and _np.dtype(dt).kind not in "fiu"):
+            raise ValueError(f"quality must be real numbers, got dtype {dt}")
+    return int(n_hyp) if pool_full is None else _chk_pool_full(pool_full)
+
+
+def _adaptive_rounds(sc, cap, conf, round_hyp, thresh, eps, max_iters, solver_opts, guided=None):
     """The rounds of ransac_pnp_batch(confidence=...): returns the state and the number of rounds.  One 4-byte read-back per round -- the
-    number of scenes still active, which the next round's solve needs as a host number (its batch size)."""
+    number of scenes still active, which the next round's solve needs as a host number (its batch size).  guided: (order, pool_full),
+    the round's minimal sets then come from sample_active_guided."""
     st = adaptive_init(sc)
     A, h0, rounds = sc.F, 0, 0
     while A > 0 and h0 < cap:
         Hr = min(round_hyp, cap - h0)
-        p2, p3, Kh = sample_active(sc, st.active, A, h0, Hr, cap)
+        if guided is None:
+            p2, p3, Kh = sample_active(sc, st.active, A, h0, Hr, cap)
+        else:
+            p2, p3, Kh = sample_active_guided(sc, st.active, A, h0, Hr, cap, guided[0], guided[1])
         res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
         count = score_active(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
         update_active(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
@@ -518,7 +643,7 @@ def _polish(sc, R, t, head, mask_pts, mask_lines, thresh):
 
 def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
                      refit_rounds: int = 1, sizes=None, device=None, polish: bool = False, confidence: Optional[float] = None, round_hyp: int = 64,
-                     **solver_opts):
+                     quality=None, pool_full: Optional[int] = None, **solver_opts):
     """Robust PnP for F scenes of different sizes in one launch sequence (what ransac_pnp does for one scene per call).
 
     Scenes: lists of F arrays pts_2d[f] [M_f,2] / pts_3d[f] [M_f,3], or packed [sum M,2] / [sum M,3] with `sizes` (a host sequence of F
@@ -534,7 +659,12 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     a minimal set is all inliers at the scene's best inlier count so far, or n_hyp.  A scene that stops after u hypotheses holds what the
     fixed budget n_hyp = u selects (same draws, lowest index on a tie); refits and polish then run over all scenes as above.  The result
     gains hyp_used [F] (host int32), rounds and confidence.  One 4-byte read-back per round on top of the call's own: the number of scenes
-    still active is the next solve's batch size, a host number."""
+    still active is the next solve's batch size, a host number.
+    quality (None: uniform draws, the code above unchanged): a matcher's score per correspondence, higher is better -- a list of F arrays
+    [M_f], or packed [sum M] with `sizes`; any real dtype.  Every scene is ranked once (rank_scenes) and hypothesis h draws its minimal
+    set from the pool_size(h, M_f, pool_full) best-ranked correspondences: 4 at h = 0, growing with h, the whole scene from h = pool_full
+    on, where the draws are the uniform ones again.  pool_full (an int >= 0) defaults to n_hyp; 0 is the uniform sampler.  With
+    confidence the stopping rule is unchanged and counts inliers of the whole scene.  The result gains pool_full."""
     szs = _check_scenes(pts_2d, pts_3d, K, sizes)
     F = len(szs)
     if confidence is not None:
@@ -549,12 +679,18 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
             raise ValueError(f"{len(seeds)} seeds for {F} scenes")
     if int(n_hyp) < 1:
         raise ValueError("n_hyp must be at least 1")
+    pool_full = _check_quality(quality, pool_full, szs, sizes is not None, n_hyp)
     sc = pack_scenes(pts_2d, pts_3d, K, sizes=szs if sizes is not None else None, device=device, seeds=seeds)
+    guided = None
+    if quality is not None:  # the ranking: once per call, before the launch sequence
+        if sizes is not None and isinstance(quality, (list, tuple)):
+            quality = _np.asarray(quality, dtype=_np.float64)
+        guided = (rank_scenes(sc, _to_dev(quality, sc.device)), pool_full)
     if confidence is not None:
-        state, rounds = _adaptive_rounds(sc, int(n_hyp), conf, round_hyp, thresh, eps, max_iters, solver_opts)
+        state, rounds = _adaptive_rounds(sc, int(n_hyp), conf, round_hyp, thresh, eps, max_iters, solver_opts, guided)
         R, t, head, mask = state.R, state.t, state.head, state.mask
     else:
-        p2, p3, Kh = sample_scenes(sc, n_hyp)
+        p2, p3, Kh = sample_scenes(sc, n_hyp) if guided is None else sample_scenes_guided(sc, n_hyp, guided[0], guided[1])
         # no torch kernel from here to the read-back: the F * n_hyp minimal solves in one launch sequence of the solver library ...
         res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
         count = score_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
@@ -572,6 +708,8 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
         out["refine"] = refined
     if confidence is not None:
         out.update(hyp_used=state.hyp_used.cpu(), rounds=rounds, confidence=conf)
+    if guided is not None:
+        out["pool_full"] = pool_full
     return out
 
 
