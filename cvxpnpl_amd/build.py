@@ -41,6 +41,7 @@ GRAD_HOST_SRC = os.path.join(HERE, "csrc", "host_vjp.cpp")
 GRAD_OUT = os.path.join(HERE, "libcvxpnpl_amd_grad.so")
 GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_grad.resources.txt")
 GRAD_DEPS = [GRAD_SRC, GRAD_HOST_SRC, os.path.join(HERE, "csrc", "vjp_core.h"), os.path.join(HERE, "csrc", "vjp_kernel.h"), os.path.join(HERE, "csrc", "solver_core.h"),
+             os.path.join(HERE, "csrc", "host_pool.h"),
              os.path.join(HERE, "csrc", "problem_io.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_grad.h")]
 
 
@@ -82,6 +83,7 @@ REFINE_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine.so")
 REFINE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine.resources.txt")
 REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"), os.path.join(HERE, "csrc", "refine_lanes.h"),
                os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+               os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine.h")]
 
 
@@ -97,6 +99,7 @@ REFINE_GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_grad.resources
 REFINE_GRAD_DEPS = [REFINE_GRAD_SRC, REFINE_GRAD_HOST_SRC, os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_vjp_kernel.h"),
                     os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                    os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
                     os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_grad.h")]
 
 
@@ -112,6 +115,7 @@ REFINE_ROBUST_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_robust.resou
 REFINE_ROBUST_DEPS = [REFINE_ROBUST_SRC, REFINE_ROBUST_HOST_SRC, os.path.join(HERE, "csrc", "refine_robust_core.h"), os.path.join(HERE, "csrc", "refine_robust_kernel.h"),
                       os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                       os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                      os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
                       os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust.h")]
 
 
@@ -129,6 +133,7 @@ REFINE_ROBUST_GRAD_DEPS = [REFINE_ROBUST_GRAD_SRC, REFINE_ROBUST_GRAD_HOST_SRC, 
                            os.path.join(HERE, "csrc", "refine_robust_kernel.h"), os.path.join(HERE, "csrc", "refine_vjp_core.h"),
                            os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                            os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                           os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
                            os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust_grad.h")]
 
 
@@ -155,7 +160,8 @@ RANSAC_GUIDED_SRC = os.path.join(HERE, "csrc", "ransac_guided_hip.hip")
 RANSAC_GUIDED_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_guided.so")
 RANSAC_GUIDED_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_guided.resources.txt")
 RANSAC_GUIDED_DEPS = [RANSAC_GUIDED_SRC, os.path.join(HERE, "csrc", "ransac_guided_kernel.h"), os.path.join(HERE, "csrc", "ransac_guided_core.h"),
-                      os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_guided.h")]
+                      os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                      os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_guided.h")]
 
 
 def ransac_guided_compile_cmd(out=RANSAC_GUIDED_OUT):

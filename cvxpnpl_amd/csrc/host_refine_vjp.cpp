@@ -1,48 +1,26 @@
 // host_refine_vjp.cpp -- host entry point of the refinement's backward pass (cvxpnpl_refine_vjp_batch_host): a threaded loop over the same
-// core (refine_vjp_core.h) as the device kernels (refine_vjp_kernel.h), so that the CPU test suite reaches the same mathematics.  Also the
-// argument checks and the error text that the device entry points (refine_grad_hip.hip, linked into the same library) share with it.
-#include <algorithm>
-#include <stdio.h>
-#include <thread>
-#include <vector>
-
+// core (refine_vjp_core.h) as the device kernels (refine_vjp_kernel.h), so that the CPU test suite reaches the same mathematics.  The
+// argument contract and the error text are refine_entry.h's; check_common holds what is this library's own, for the device entry points
+// (refine_grad_hip.hip, linked into the same library) too.
 #include "../../include/cvxpnpl_amd_refine_grad.h"
+#include "refine_entry.h"
 #include "refine_vjp_core.h"
 
 namespace cvxrg {
 
-// (hidden: the library exports what its header declares and nothing else; refine_grad_hip.hip declares the same three)
-__attribute__((visibility("hidden"))) char *err_buf();
-__attribute__((visibility("hidden"))) int bad_args(const char *who, const char *what);
+// K and the poses, the status output, the status column: what the three entry points check once the sizes are known to be positive
 __attribute__((visibility("hidden"))) int check_common(const char *who, int32_t K_per, const double *K, const double *R, const double *t,
-                                                       const int32_t *status, int64_t status_stride, const void *vjp_status);
-
-char *err_buf()
+                                                       const int32_t *status, int64_t status_stride, const void *vjp_status)
 {
-    static thread_local char buf[512] = "";
-    return buf;
-}
-
-int bad_args(const char *who, const char *what)
-{
-    snprintf(err_buf(), 512, "%s: bad arguments (%s)", who, what);
-    return -1;
-}
-
-// what the three entry points share once the sizes are known to be positive
-int check_common(const char *who, int32_t K_per, const double *K, const double *R, const double *t, const int32_t *status, int64_t status_stride,
-                 const void *vjp_status)
-{
-    if (K_per != 0 && K_per != 1) return bad_args(who, "K_per_problem / K_per_scene is 0 or 1");
-    if (!K || !R || !t) return bad_args(who, "K, R or t is null");
-    if (!vjp_status) return bad_args(who, "vjp_status is null");
-    if (status && status_stride < 0) return bad_args(who, "negative status_stride");
+    if (const char *m = cvxre::check_pose(K_per, K, R, t)) return cvxre::bad_args(who, m);
+    if (!vjp_status) return cvxre::bad_args(who, "vjp_status is null");
+    if (const char *m = cvxre::check_status(status, status_stride)) return cvxre::bad_args(who, m);
     return 0;
 }
 
 } // namespace cvxrg
 
-extern "C" const char *cvxpnpl_refine_grad_last_error(void) { return cvxrg::err_buf(); }
+extern "C" const char *cvxpnpl_refine_grad_last_error(void) { return cvxre::err_buf(); }
 
 extern "C" const char *cvxpnpl_refine_grad_version(void) { return "cvxpnpl_amd_refine_grad 1"; }
 
@@ -53,38 +31,21 @@ extern "C" int cvxpnpl_refine_vjp_batch_host(int64_t batch, int32_t n_p, const d
                                              double *g_line_2d, double *g_line_3d, int32_t *vjp_status, double *info, int32_t n_threads)
 {
     const char *who = "cvxpnpl_refine_vjp_batch_host";
-    if (batch < 0 || n_p < 0 || n_l < 0 || (int64_t)n_p + n_l > 0x7fffffffLL) return cvxrg::bad_args(who, "negative size");
+    if (const char *m = cvxre::check_sizes(batch, n_p, n_l, INT32_MAX)) return cvxre::bad_args(who, m);
     if (batch == 0) return 0;
-    if ((n_p > 0 && (!pts_2d || !pts_3d)) || (n_l > 0 && (!line_2d || !line_3d))) return cvxrg::bad_args(who, "a correspondence pointer is null");
+    if (const char *m = cvxre::check_pairs(n_p, pts_2d, pts_3d, n_l, line_2d, line_3d)) return cvxre::bad_args(who, m);
     if (int rc = cvxrg::check_common(who, K_per_problem, K, R, t, refine_status, status_stride, vjp_status)) return rc;
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if ((int64_t)nt > batch) nt = (int)batch;
-    auto work = [&](int64_t lo, int64_t hi) {
+    cvxh::for_chunks(batch, n_threads, [&](int64_t lo, int64_t hi) {
         for (int64_t b = lo; b < hi; ++b) {
-            const cvx::ProblemView pv = cvx::make_view(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem);
             cvxr::HostLanes ln;
-            ln.pb.n_p = n_p; ln.pb.n_l = n_l;
-            ln.pb.p2 = pv.p2; ln.pb.p3 = pv.p3; ln.pb.l2 = pv.l2; ln.pb.l3 = pv.l3;
-            ln.pb.mp = mask_pts && n_p > 0 ? mask_pts + b * n_p : nullptr;
-            ln.pb.ml = mask_lines && n_l > 0 ? mask_lines + b * n_l : nullptr;
-            const bool admit = !refine_status || cvxr::admitted(refine_status[b * status_stride], admit_mask);
+            bool admit;
+            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, refine_status, status_stride,
+                                                            admit_mask, mask_pts, mask_lines, ln.pb, admit);
             cvxrg::Grads g;
-            g.p2 = g_pts_2d && n_p > 0 ? g_pts_2d + b * n_p * 2 : nullptr;
-            g.p3 = g_pts_3d && n_p > 0 ? g_pts_3d + b * n_p * 3 : nullptr;
-            g.l2 = g_line_2d && n_l > 0 ? g_line_2d + b * n_l * 4 : nullptr;
-            g.l3 = g_line_3d && n_l > 0 ? g_line_3d + b * n_l * 6 : nullptr;
+            cvxre::host_grads(g, b, n_p, n_l, g_pts_2d, g_pts_3d, g_line_2d, g_line_3d);
             vjp_status[b] = cvxrg::vjp_problem(ln, 0, 1, pv.K, R + 9 * b, t + 3 * b, grad_R ? grad_R + 9 * b : nullptr, grad_t ? grad_t + 3 * b : nullptr,
                                                admit, true, g, info ? info + 2 * b : nullptr);
         }
-    };
-    if (nt == 1) { work(0, batch); return 0; }
-    std::vector<std::thread> pool;
-    const int64_t chunk = (batch + nt - 1) / nt;
-    for (int k = 0; k < nt; ++k) {
-        const int64_t lo = k * chunk, hi = std::min<int64_t>(batch, lo + chunk);
-        if (lo < hi) pool.emplace_back(work, lo, hi);
-    }
-    for (auto &th : pool) th.join();
+    });
     return 0;
 }

@@ -1,10 +1,9 @@
 // host_vjp.cpp -- host entry point of the pose VJP (cvxpnpl_pose_vjp_host): a threaded loop over the same core (vjp_core.h) as the
 // device kernels (vjp_kernel.h), so that the CPU test suite can check the mathematics against finite differences.
 #include <algorithm>
-#include <thread>
-#include <vector>
 
 #include "../../include/cvxpnpl_amd_grad.h"
+#include "host_pool.h"
 #include "vjp_core.h"
 
 namespace {
@@ -27,10 +26,7 @@ extern "C" int cvxpnpl_pose_vjp_host(int64_t batch, int32_t n_p, const double *p
     if (batch < 0 || n_p < 0 || n_l < 0 || (n_p == 0 && n_l == 0) || !K || !R || !t || !vjp_status || (n_p > 0 && (!pts_2d || !pts_3d)) ||
         (n_l > 0 && (!line_2d || !line_3d)))
         return -1;
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if ((int64_t)nt > batch) nt = batch > 0 ? (int)batch : 1;
-    auto work = [&](int64_t lo, int64_t hi) {
+    cvxh::for_chunks(batch, n_threads, [&](int64_t lo, int64_t hi) {
         for (int64_t b = lo; b < hi; ++b) {
             const cvx::ProblemView pv = cvx::make_view(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem);
             double info[2] = {NAN, NAN};
@@ -61,14 +57,6 @@ extern "C" int cvxpnpl_pose_vjp_host(int64_t batch, int32_t n_p, const double *p
                 cvxv::vjp_line(fr, v, pv.l2 + 4 * i, pv.l3 + 6 * i, g_line_2d ? g_line_2d + (b * n_l + i) * 4 : nullptr,
                                g_line_3d ? g_line_3d + (b * n_l + i) * 6 : nullptr);
         }
-    };
-    if (nt == 1) { work(0, batch); return 0; }
-    std::vector<std::thread> pool;
-    const int64_t chunk = (batch + nt - 1) / nt;
-    for (int k = 0; k < nt; ++k) {
-        const int64_t lo = k * chunk, hi = std::min<int64_t>(batch, lo + chunk);
-        if (lo < hi) pool.emplace_back(work, lo, hi);
-    }
-    for (auto &th : pool) th.join();
+    });
     return 0;
 }

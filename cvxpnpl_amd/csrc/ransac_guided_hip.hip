@@ -5,11 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include <algorithm>
-#include <thread>
-#include <vector>
-
 #include "../../include/cvxpnpl_amd_ransac_guided.h"
+#include "host_pool.h"
 #include "ransac_guided_kernel.h"
 
 namespace {
@@ -89,10 +86,7 @@ extern "C" int cvxpnpl_ransac_guided_rank_host(int64_t n_scenes, const int64_t *
     if (!offsets) return bad(who, "offsets is null");
     if (!quality) return bad(who, "quality is null");
     if (!order) return bad(who, "order is null");
-    int nt = n_threads > 0 ? n_threads : (int)std::thread::hardware_concurrency();
-    if (nt < 1) nt = 1;
-    if ((int64_t)nt > n_scenes) nt = (int)n_scenes;
-    auto work = [&](int64_t lo, int64_t hi) {
+    cvxh::for_chunks(n_scenes, n_threads, [&](int64_t lo, int64_t hi) {
         for (int64_t f = lo; f < hi; ++f) {
             int64_t beg, n;
             host_slice(offsets, f, n_total, beg, n);
@@ -104,15 +98,7 @@ extern "C" int cvxpnpl_ransac_guided_rank_host(int64_t n_scenes, const int64_t *
                 order[beg + rank] = (int32_t)m;
             }
         }
-    };
-    if (nt == 1) { work(0, n_scenes); return 0; }
-    std::vector<std::thread> pool;
-    const int64_t chunk = (n_scenes + nt - 1) / nt;
-    for (int k = 0; k < nt; ++k) {
-        const int64_t lo = k * chunk, hi = std::min<int64_t>(n_scenes, lo + chunk);
-        if (lo < hi) pool.emplace_back(work, lo, hi);
-    }
-    for (auto &th : pool) th.join();
+    });
     return 0;
 }
 

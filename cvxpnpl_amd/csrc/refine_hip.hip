@@ -1,36 +1,22 @@
 // refine_hip.hip -- device entry points of the reprojection refinement (include/cvxpnpl_amd_refine.h), built as libcvxpnpl_amd_refine.so.
 // The kernels are refine_kernel.h, the mathematics refine_core.h (shared with the host entry point, host_refine.cpp, which is linked into
-// the same library and holds the argument checks).  Every entry point checks its arguments before it launches anything.
+// the same library).  The argument contract is refine_entry.h's, the library's own checks host_refine.cpp's check_common.  Every entry
+// point checks its arguments before it launches anything.
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/cvxpnpl_amd_refine.h"
+#include "refine_entry.h"
 #include "refine_kernel.h"
 
 namespace cvxr {
 
 // (defined in host_refine.cpp)
-__attribute__((visibility("hidden"))) char *err_buf();
-__attribute__((visibility("hidden"))) int bad_args(const char *who, const char *what);
-__attribute__((visibility("hidden"))) int check_common(const char *who, int64_t n, int32_t K_per, const double *K, const double *R, const double *t,
+__attribute__((visibility("hidden"))) int check_common(const char *who, int32_t K_per, const double *K, const double *R, const double *t,
                                                        const int32_t *status, int64_t status_stride, const cvxpnpl_refine_opts_t *opts, const void *R_out,
                                                        const void *t_out, const void *cost, const void *iters, const void *status_out, const void *n_live,
                                                        Opts &o);
 
 } // namespace cvxr
-
-namespace {
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(cvxr::err_buf(), 512, "%s: %s", what, hipGetErrorString(e));
-    return -2;
-}
-
-} // namespace
 
 extern "C" int cvxpnpl_refine_batch(int64_t batch, int32_t n_p, const double *d_pts_2d, const double *d_pts_3d, int32_t n_l, const double *d_line_2d,
                                     const double *d_line_3d, const double *d_K, int32_t K_per_problem, const double *d_R, const double *d_t,
@@ -39,18 +25,17 @@ extern "C" int cvxpnpl_refine_batch(int64_t batch, int32_t n_p, const double *d_
                                     int32_t *d_iters, int32_t *d_status_out, int32_t *d_n_live, double *d_cov, void *stream)
 {
     const char *who = "cvxpnpl_refine_batch";
-    if (batch < 0 || n_p < 0 || n_l < 0 || (int64_t)n_p + n_l > 0x7fffffffLL) return cvxr::bad_args(who, "negative size");
+    if (const char *m = cvxre::check_sizes(batch, n_p, n_l, INT32_MAX)) return cvxre::bad_args(who, m);
     if (batch == 0) return 0;
-    if ((n_p > 0 && (!d_pts_2d || !d_pts_3d)) || (n_l > 0 && (!d_line_2d || !d_line_3d))) return cvxr::bad_args(who, "a correspondence pointer is null");
+    if (const char *m = cvxre::check_pairs(n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d)) return cvxre::bad_args(who, m);
     cvxr::BatchArgs a;
-    if (int rc = cvxr::check_common(who, batch, K_per_problem, d_K, d_R, d_t, d_status, status_stride, opts, d_R_out, d_t_out, d_cost, d_iters, d_status_out,
+    if (int rc = cvxr::check_common(who, K_per_problem, d_K, d_R, d_t, d_status, status_stride, opts, d_R_out, d_t_out, d_cost, d_iters, d_status_out,
                                     d_n_live, a.opts))
         return rc;
-    const int64_t grid = (batch + cvxr::TPB / 16 - 1) / (cvxr::TPB / 16);
-    if (grid > 0x7fffffffLL) return cvxr::bad_args(who, "batch too large for one launch");
-    a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.K_per_problem = K_per_problem; a.admit = admit_mask; a.status_stride = status_stride;
-    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.K = d_K; a.R = d_R; a.t = d_t; a.status = d_status;
-    a.mp = n_p > 0 ? d_mask_pts : nullptr; a.ml = n_l > 0 ? d_mask_lines : nullptr;
+    int64_t grid;
+    if (const char *m = cvxre::check_batch_grid(batch, cvxr::TPB / 16, grid)) return cvxre::bad_args(who, m);
+    cvxre::fill_batch(a, batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K, K_per_problem, d_R, d_t, d_status, status_stride, admit_mask,
+                      d_mask_pts, d_mask_lines);
     a.out.R = d_R_out; a.out.t = d_t_out; a.out.cost = d_cost; a.out.cov = d_cov; a.out.iters = d_iters; a.out.status = d_status_out; a.out.n_live = d_n_live;
     const int ncorr = n_p + n_l;
     const dim3 g((unsigned)grid), blk(cvxr::TPB);
@@ -61,7 +46,7 @@ extern "C" int cvxpnpl_refine_batch(int64_t batch, int32_t n_p, const double *d_
     else if (ncorr <= 64) hipLaunchKernelGGL(cvxr::refine_group_kernel<4>, g, blk, 0, s, a);
     else hipLaunchKernelGGL(cvxr::refine_group_kernel<0>, g, blk, 0, s, a);
     if (d_cov) hipLaunchKernelGGL(cvxr::cov_group_kernel, g, blk, 0, s, a); // (reads what the launch before it wrote)
-    return launched("refine_group_kernel launch");
+    return cvxre::launched("refine_group_kernel launch");
 }
 
 extern "C" int cvxpnpl_refine_scenes(int64_t n_scenes, const int64_t *d_pt_offsets, int64_t n_pts, const int64_t *d_ln_offsets, int64_t n_lines,
@@ -72,22 +57,20 @@ extern "C" int cvxpnpl_refine_scenes(int64_t n_scenes, const int64_t *d_pt_offse
                                      double *d_cov, void *stream)
 {
     const char *who = "cvxpnpl_refine_scenes";
-    if (n_scenes < 0 || n_pts < 0 || n_lines < 0) return cvxr::bad_args(who, "negative size");
+    if (const char *m = cvxre::check_sizes(n_scenes, n_pts, n_lines)) return cvxre::bad_args(who, m);
     if (n_scenes == 0) return 0;
-    if (!d_pt_offsets || (n_lines > 0 && !d_ln_offsets)) return cvxr::bad_args(who, "d_pt_offsets or d_ln_offsets is null");
-    if ((n_pts > 0 && (!d_pts_2d || !d_pts_3d)) || (n_lines > 0 && (!d_line_2d || !d_line_3d))) return cvxr::bad_args(who, "a correspondence pointer is null");
+    if (const char *m = cvxre::check_scenes(d_pt_offsets, n_pts, d_ln_offsets, n_lines, d_pts_2d, d_pts_3d, d_line_2d, d_line_3d))
+        return cvxre::bad_args(who, m);
     cvxr::SceneArgs a;
-    if (int rc = cvxr::check_common(who, n_scenes, K_per_scene, d_K, d_R, d_t, d_status, status_stride, opts, d_R_out, d_t_out, d_cost, d_iters, d_status_out,
-                                    d_n_live, a.opts))
+    if (int rc = cvxr::check_common(who, K_per_scene, d_K, d_R, d_t, d_status, status_stride, opts, d_R_out, d_t_out, d_cost, d_iters, d_status_out, d_n_live,
+                                    a.opts))
         return rc;
-    if (n_scenes > 0x7fffffffLL) return cvxr::bad_args(who, "too many scenes for one launch");
-    a.n_scenes = n_scenes; a.n_pts = n_pts; a.n_lines = n_lines; a.off_p = d_pt_offsets; a.off_l = n_lines > 0 ? d_ln_offsets : nullptr;
-    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.K = d_K; a.R = d_R; a.t = d_t; a.K_per_scene = K_per_scene;
-    a.admit = admit_mask; a.status_stride = status_stride; a.status = d_status;
-    a.mp = n_pts > 0 ? d_mask_pts : nullptr; a.ml = n_lines > 0 ? d_mask_lines : nullptr;
+    if (const char *m = cvxre::check_scenes_grid(n_scenes)) return cvxre::bad_args(who, m);
+    cvxre::fill_scenes(a, n_scenes, d_pt_offsets, n_pts, d_ln_offsets, n_lines, d_pts_2d, d_pts_3d, d_line_2d, d_line_3d, d_K, K_per_scene, d_R, d_t,
+                       d_status, status_stride, admit_mask, d_mask_pts, d_mask_lines);
     a.out.R = d_R_out; a.out.t = d_t_out; a.out.cost = d_cost; a.out.cov = d_cov; a.out.iters = d_iters; a.out.status = d_status_out; a.out.n_live = d_n_live;
     const dim3 g((unsigned)n_scenes), blk(cvxr::TPB);
     hipLaunchKernelGGL(cvxr::refine_scenes_kernel, g, blk, 0, (hipStream_t)stream, a);
     if (d_cov) hipLaunchKernelGGL(cvxr::cov_scenes_kernel, g, blk, 0, (hipStream_t)stream, a); // (reads what the launch before it wrote)
-    return launched("refine_scenes_kernel launch");
+    return cvxre::launched("refine_scenes_kernel launch");
 }

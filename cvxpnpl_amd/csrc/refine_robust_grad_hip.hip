@@ -1,36 +1,22 @@
 // refine_robust_grad_hip.hip -- device entry points of the robust refinement's backward pass (include/cvxpnpl_amd_refine_robust_grad.h),
 // built as libcvxpnpl_amd_refine_robust_grad.so.  The kernels are refine_robust_vjp_kernel.h, the mathematics refine_robust_vjp_core.h
-// (shared with the host entry point, host_refine_robust_vjp.cpp, which is linked into the same library and holds the argument checks).
-// Every entry point checks its arguments before it launches anything.
+// (shared with the host entry point, host_refine_robust_vjp.cpp, which is linked into the same library).  The argument contract is
+// refine_entry.h's, the library's own checks host_refine_robust_vjp.cpp's check_common.  Every entry point checks its arguments before it
+// launches anything.
 #include <hip/hip_runtime.h>
-#include <stdint.h>
-#include <stdio.h>
 
 #include "../../include/cvxpnpl_amd_refine_robust_grad.h"
+#include "refine_entry.h"
 #include "refine_robust_vjp_kernel.h"
 
 namespace cvxrbg {
 
 // (defined in host_refine_robust_vjp.cpp)
-__attribute__((visibility("hidden"))) char *err_buf();
-__attribute__((visibility("hidden"))) int bad_args(const char *who, const char *what);
 __attribute__((visibility("hidden"))) int check_common(const char *who, int32_t K_per, const double *K, const double *R, const double *t,
                                                        const int32_t *status, int64_t status_stride, int32_t loss, double scale_px,
                                                        const void *vjp_status);
 
 } // namespace cvxrbg
-
-namespace {
-
-int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(cvxrbg::err_buf(), 512, "%s: %s", what, hipGetErrorString(e));
-    return -2;
-}
-
-} // namespace
 
 extern "C" int cvxpnpl_refine_robust_vjp_batch(int64_t batch, int32_t n_p, const double *d_pts_2d, const double *d_pts_3d, int32_t n_l,
                                                const double *d_line_2d, const double *d_line_3d, const double *d_K, int32_t K_per_problem,
@@ -42,17 +28,16 @@ extern "C" int cvxpnpl_refine_robust_vjp_batch(int64_t batch, int32_t n_p, const
                                                void *stream)
 {
     const char *who = "cvxpnpl_refine_robust_vjp_batch";
-    if (batch < 0 || n_p < 0 || n_l < 0 || (int64_t)n_p + n_l > 0x7fffffffLL) return cvxrbg::bad_args(who, "negative size");
+    if (const char *m = cvxre::check_sizes(batch, n_p, n_l, INT32_MAX)) return cvxre::bad_args(who, m);
     if (batch == 0) return 0;
-    if ((n_p > 0 && (!d_pts_2d || !d_pts_3d)) || (n_l > 0 && (!d_line_2d || !d_line_3d))) return cvxrbg::bad_args(who, "a correspondence pointer is null");
+    if (const char *m = cvxre::check_pairs(n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d)) return cvxre::bad_args(who, m);
     if (int rc = cvxrbg::check_common(who, K_per_problem, d_K, d_R, d_t, d_refine_status, status_stride, loss, scale_px, d_vjp_status)) return rc;
-    const int64_t grid = (batch + cvxr::TPB / 16 - 1) / (cvxr::TPB / 16);
-    if (grid > 0x7fffffffLL) return cvxrbg::bad_args(who, "batch too large for one launch");
+    int64_t grid;
+    if (const char *m = cvxre::check_batch_grid(batch, cvxr::TPB / 16, grid)) return cvxre::bad_args(who, m);
     cvxrbg::VjpBatchArgs a;
-    a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.K_per_problem = K_per_problem; a.admit = admit_mask; a.status_stride = status_stride;
-    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.K = d_K; a.R = d_R; a.t = d_t; a.gR = d_grad_R; a.gt = d_grad_t;
-    a.status = d_refine_status;
-    a.mp = n_p > 0 ? d_mask_pts : nullptr; a.ml = n_l > 0 ? d_mask_lines : nullptr;
+    cvxre::fill_batch(a, batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K, K_per_problem, d_R, d_t, d_refine_status, status_stride,
+                      admit_mask, d_mask_pts, d_mask_lines);
+    a.gR = d_grad_R; a.gt = d_grad_t;
     a.wp = n_p > 0 ? d_w_pts : nullptr; a.wl = n_l > 0 ? d_w_lines : nullptr;
     a.loss = cvxrb::make_loss(loss, scale_px);
     a.g_p2 = n_p > 0 ? d_g_pts_2d : nullptr; a.g_p3 = n_p > 0 ? d_g_pts_3d : nullptr;
@@ -67,7 +52,7 @@ extern "C" int cvxpnpl_refine_robust_vjp_batch(int64_t batch, int32_t n_p, const
     else if (ncorr <= 32) hipLaunchKernelGGL(cvxrbg::refine_robust_vjp_group_kernel<2>, g, blk, 0, s, a);
     else if (ncorr <= 64) hipLaunchKernelGGL(cvxrbg::refine_robust_vjp_group_kernel<4>, g, blk, 0, s, a);
     else hipLaunchKernelGGL(cvxrbg::refine_robust_vjp_group_kernel<0>, g, blk, 0, s, a);
-    return launched("refine_robust_vjp_group_kernel launch");
+    return cvxre::launched("refine_robust_vjp_group_kernel launch");
 }
 
 extern "C" int cvxpnpl_refine_robust_vjp_scenes(int64_t n_scenes, const int64_t *d_pt_offsets, int64_t n_pts, const int64_t *d_ln_offsets,
@@ -80,17 +65,15 @@ extern "C" int cvxpnpl_refine_robust_vjp_scenes(int64_t n_scenes, const int64_t 
                                                 int32_t *d_vjp_status, double *d_info, void *stream)
 {
     const char *who = "cvxpnpl_refine_robust_vjp_scenes";
-    if (n_scenes < 0 || n_pts < 0 || n_lines < 0) return cvxrbg::bad_args(who, "negative size");
+    if (const char *m = cvxre::check_sizes(n_scenes, n_pts, n_lines)) return cvxre::bad_args(who, m);
     if (n_scenes == 0) return 0;
-    if (!d_pt_offsets || (n_lines > 0 && !d_ln_offsets)) return cvxrbg::bad_args(who, "d_pt_offsets or d_ln_offsets is null");
-    if ((n_pts > 0 && (!d_pts_2d || !d_pts_3d)) || (n_lines > 0 && (!d_line_2d || !d_line_3d))) return cvxrbg::bad_args(who, "a correspondence pointer is null");
+    if (const char *m = cvxre::check_scenes(d_pt_offsets, n_pts, d_ln_offsets, n_lines, d_pts_2d, d_pts_3d, d_line_2d, d_line_3d))
+        return cvxre::bad_args(who, m);
     if (int rc = cvxrbg::check_common(who, K_per_scene, d_K, d_R, d_t, d_refine_status, status_stride, loss, scale_px, d_vjp_status)) return rc;
-    if (n_scenes > 0x7fffffffLL) return cvxrbg::bad_args(who, "too many scenes for one launch");
+    if (const char *m = cvxre::check_scenes_grid(n_scenes)) return cvxre::bad_args(who, m);
     cvxrbg::VjpSceneArgs a;
-    a.n_scenes = n_scenes; a.n_pts = n_pts; a.n_lines = n_lines; a.off_p = d_pt_offsets; a.off_l = n_lines > 0 ? d_ln_offsets : nullptr;
-    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.K = d_K; a.R = d_R; a.t = d_t; a.K_per_scene = K_per_scene;
-    a.admit = admit_mask; a.status_stride = status_stride; a.status = d_refine_status;
-    a.mp = n_pts > 0 ? d_mask_pts : nullptr; a.ml = n_lines > 0 ? d_mask_lines : nullptr;
+    cvxre::fill_scenes(a, n_scenes, d_pt_offsets, n_pts, d_ln_offsets, n_lines, d_pts_2d, d_pts_3d, d_line_2d, d_line_3d, d_K, K_per_scene, d_R, d_t,
+                       d_refine_status, status_stride, admit_mask, d_mask_pts, d_mask_lines);
     a.wp = n_pts > 0 ? d_w_pts : nullptr; a.wl = n_lines > 0 ? d_w_lines : nullptr;
     a.loss_kind = loss; a.scale_px = loss == cvxrb::LOSS_L2 ? 1.0 : scale_px;
     a.gR = d_grad_R; a.gt = d_grad_t;
@@ -99,5 +82,5 @@ extern "C" int cvxpnpl_refine_robust_vjp_scenes(int64_t n_scenes, const int64_t 
     a.g_wp = n_pts > 0 ? d_g_w_pts : nullptr; a.g_wl = n_lines > 0 ? d_g_w_lines : nullptr;
     a.info = d_info; a.vstatus = d_vjp_status;
     hipLaunchKernelGGL(cvxrbg::refine_robust_vjp_scenes_kernel, dim3((unsigned)n_scenes), dim3(cvxr::TPB), 0, (hipStream_t)stream, a);
-    return launched("refine_robust_vjp_scenes_kernel launch");
+    return cvxre::launched("refine_robust_vjp_scenes_kernel launch");
 }

@@ -19,8 +19,9 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._refine_args import _chk_admit, _cp, batch_args, grad_outputs, host_args, scene_args
 from .api import _ptr, _require_gpu
-from .refine import ADMIT_USABLE, _chk, _chk_status, _cp, _np64, _opts, _pair, refine_pose_batch
+from .refine import ADMIT_USABLE, _opts, refine_pose_batch
 
 __all__ = ["refine_vjp", "refine_vjp_scenes", "refine_vjp_host", "refine_pose_batch_diff", "pose_passthrough", "ADMIT_CONVERGED", "GRAD_NAMES"]
 
@@ -36,13 +37,6 @@ def _chk_want(want):
     return want
 
 
-def _chk_admit(admit_mask):
-    admit_mask = int(admit_mask)
-    if admit_mask < 0 or admit_mask > 0xFFFFFFFF:
-        raise ValueError("admit_mask: a 32-bit mask of refine statuses")
-    return admit_mask
-
-
 def refine_vjp(R, t, status, grad_R=None, grad_t=None, pts_2d=None, line_2d=None, pts_3d=None, line_3d=None, K=None,
                admit_mask: int = ADMIT_CONVERGED, mask_pts=None, mask_lines=None, want=GRAD_NAMES, want_info: bool = False):
     """dL/d(correspondences) of B refined poses from dL/dR [B,3,3] and dL/dt [B,3] (either may be None: zero), at the poses R, t with the
@@ -53,43 +47,18 @@ def refine_vjp(R, t, status, grad_R=None, grad_t=None, pts_2d=None, line_2d=None
     records or the pose is not a strict minimum --, 3 a live record behind the camera or not finite; for 1-3 every gradient is zero) and,
     with want_info, ``info`` [B,2]: |g| / sum |J||rho| (the stationarity of the pose handed in) and the smallest Cholesky pivot ratio."""
     want, admit_mask = _chk_want(want), _chk_admit(admit_mask)
-    if not isinstance(R, torch.Tensor) or R.dim() != 3:
-        raise ValueError("R: expected a torch tensor [B,3,3]")
-    B, dev = int(R.shape[0]), R.device
-    _chk(R, "R", torch.float64, (B, 3, 3), dev)
-    _chk(t, "t", torch.float64, (B, 3), dev)
-    if grad_R is not None:
-        _chk(grad_R, "grad_R", torch.float64, (B, 3, 3), dev)
-    if grad_t is not None:
-        _chk(grad_t, "grad_t", torch.float64, (B, 3), dev)
-    p2, p3, n_p = _pair(pts_2d, pts_3d, "points", (2,), (3,), dev, B)
-    l2, l3, n_l = _pair(line_2d, line_3d, "lines", (2, 2), (2, 3), dev, B)
-    if n_p == 0 and n_l == 0:
-        raise ValueError("need at least one point or line correspondence")
-    if not isinstance(K, torch.Tensor) or tuple(K.shape) not in ((3, 3), (B, 3, 3)):
-        raise ValueError(f"K must be a tensor [3,3] or [{B},3,3]")
-    per = int(K.dim() == 3)
-    _chk(K, "K", torch.float64, (B, 3, 3) if per else (3, 3), dev)
-    st, stride = _chk_status(status, B, dev)
-    if mask_pts is not None:
-        _chk(mask_pts, "mask_pts", torch.uint8, (B, n_p), dev)
-    if mask_lines is not None:
-        _chk(mask_lines, "mask_lines", torch.uint8, (B, n_l), dev)
-    if dev.type != "cuda":
-        raise ValueError(f"the poses are on {dev}: cvxpnpl_amd has no CPU path (refine_vjp_host is the host form)")
+    a = batch_args("refine_vjp_host", R, t, pts_2d, line_2d, pts_3d, line_3d, K, status, mask_pts, mask_lines, grad_R=grad_R, grad_t=grad_t)
     _require_gpu()
     L = _lib.refine_grad_lib()
+    B, dev = a.B, a.dev
     f64 = dict(dtype=torch.float64, device=dev)
-    out = {"pts_2d": torch.empty((B, n_p, 2), **f64) if n_p and "pts_2d" in want else None,
-           "pts_3d": torch.empty((B, n_p, 3), **f64) if n_p and "pts_3d" in want else None,
-           "line_2d": torch.empty((B, n_l, 2, 2), **f64) if n_l and "line_2d" in want else None,
-           "line_3d": torch.empty((B, n_l, 2, 3), **f64) if n_l and "line_3d" in want else None}
+    out = grad_outputs(want, (B, a.n_p), (B, a.n_l), lambda shape: torch.empty(shape, **f64))
     vst = torch.empty(B, dtype=torch.int32, device=dev)
     info = torch.empty((B, 2), **f64) if want_info else None
     with torch.cuda.device(dev):
-        rc = L.cvxpnpl_refine_vjp_batch(B, n_p, _ptr(p2), _ptr(p3), n_l, _ptr(l2), _ptr(l3), _ptr(K), per, _ptr(R), _ptr(t), _ptr(st), stride, admit_mask,
-                                        _ptr(mask_pts), _ptr(mask_lines), _ptr(grad_R), _ptr(grad_t), _ptr(out["pts_2d"]), _ptr(out["pts_3d"]),
-                                        _ptr(out["line_2d"]), _ptr(out["line_3d"]), _ptr(vst), _ptr(info),
+        rc = L.cvxpnpl_refine_vjp_batch(B, a.n_p, _ptr(a.p2), _ptr(a.p3), a.n_l, _ptr(a.l2), _ptr(a.l3), _ptr(K), a.per, _ptr(R), _ptr(t), _ptr(a.st),
+                                        a.stride, admit_mask, _ptr(mask_pts), _ptr(mask_lines), _ptr(grad_R), _ptr(grad_t), _ptr(out["pts_2d"]),
+                                        _ptr(out["pts_3d"]), _ptr(out["line_2d"]), _ptr(out["line_3d"]), _ptr(vst), _ptr(info),
                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise RuntimeError(f"cvxpnpl_refine_vjp_batch failed ({rc}): {L.cvxpnpl_refine_grad_last_error().decode()}")
@@ -105,43 +74,21 @@ def refine_vjp_scenes(sc, R, t, status, grad_R=None, grad_t=None, mask_pts=None,
     ``refine_scenes`` returned: R [F,3,3], t [F,3], status [F] int32 or None, grad_R / grad_t the upstream gradients, mask_pts [sum P] /
     mask_lines [sum L] uint8 as the refinement was given them.  The gradients come in the packed layouts [sum P,2], [sum P,3],
     [sum L,2,2], [sum L,2,3] (records that belong to no scene get zero).  One workgroup per scene, one launch, no synchronisation."""
-    from . import ransac as _rn
-
     want, admit_mask = _chk_want(want), _chk_admit(admit_mask)
-    lines = isinstance(sc, _rn.PnplScenes)
-    if not lines and not isinstance(sc, _rn.Scenes):
-        raise ValueError("sc: expected ransac.Scenes or ransac.PnplScenes")
-    (_rn._chk_pnpl_scenes if lines else _rn._chk_scenes)(sc)
-    F, dev = sc.F, sc.device
-    _chk(R, "R", torch.float64, (F, 3, 3), dev)
-    _chk(t, "t", torch.float64, (F, 3), dev)
-    if grad_R is not None:
-        _chk(grad_R, "grad_R", torch.float64, (F, 3, 3), dev)
-    if grad_t is not None:
-        _chk(grad_t, "grad_t", torch.float64, (F, 3), dev)
-    st, stride = _chk_status(status, F, dev)
-    n_pts, n_lines = sc.total, (sc.line_total if lines else 0)
-    if mask_pts is not None:
-        _chk(mask_pts, "mask_pts", torch.uint8, (n_pts,), dev)
-    if mask_lines is not None:
-        if not lines:
-            raise ValueError("mask_lines given for scenes without lines")
-        _chk(mask_lines, "mask_lines", torch.uint8, (n_lines,), dev)
+    a = scene_args(sc, R, t, status, mask_pts, mask_lines, grad_R=grad_R, grad_t=grad_t)
     _require_gpu()
     L = _lib.refine_grad_lib()
+    F, dev = a.F, a.dev
     f64 = dict(dtype=torch.float64, device=dev)
-    out = {"pts_2d": torch.zeros((n_pts, 2), **f64) if n_pts and "pts_2d" in want else None,
-           "pts_3d": torch.zeros((n_pts, 3), **f64) if n_pts and "pts_3d" in want else None,
-           "line_2d": torch.zeros((n_lines, 2, 2), **f64) if n_lines and "line_2d" in want else None,
-           "line_3d": torch.zeros((n_lines, 2, 3), **f64) if n_lines and "line_3d" in want else None}
+    # (zeros: a record outside every scene's slice is written by no workgroup)
+    out = grad_outputs(want, (a.n_pts,), (a.n_lines,), lambda shape: torch.zeros(shape, **f64))
     vst = torch.empty(F, dtype=torch.int32, device=dev)
     info = torch.empty((F, 2), **f64) if want_info else None
     with torch.cuda.device(dev):
-        rc = L.cvxpnpl_refine_vjp_scenes(F, _ptr(sc.offsets), n_pts, _ptr(sc.line_offsets) if lines else None, n_lines, _ptr(sc.x), _ptr(sc.X),
-                                         _ptr(sc.l2) if lines else None, _ptr(sc.l3) if lines else None, _ptr(sc.K), sc.per_scene_K, _ptr(R), _ptr(t),
-                                         _ptr(st), stride, admit_mask, _ptr(mask_pts), _ptr(mask_lines), _ptr(grad_R), _ptr(grad_t), _ptr(out["pts_2d"]),
-                                         _ptr(out["pts_3d"]), _ptr(out["line_2d"]), _ptr(out["line_3d"]), _ptr(vst), _ptr(info),
-                                         C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = L.cvxpnpl_refine_vjp_scenes(F, _ptr(sc.offsets), a.n_pts, _ptr(a.off_l), a.n_lines, _ptr(sc.x), _ptr(sc.X), _ptr(a.l2), _ptr(a.l3), _ptr(sc.K),
+                                         sc.per_scene_K, _ptr(R), _ptr(t), _ptr(a.st), a.stride, admit_mask, _ptr(mask_pts), _ptr(mask_lines),
+                                         _ptr(grad_R), _ptr(grad_t), _ptr(out["pts_2d"]), _ptr(out["pts_3d"]), _ptr(out["line_2d"]), _ptr(out["line_3d"]),
+                                         _ptr(vst), _ptr(info), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise RuntimeError(f"cvxpnpl_refine_vjp_scenes failed ({rc}): {L.cvxpnpl_refine_grad_last_error().decode()}")
     out["vjp_status"] = vst
@@ -156,48 +103,14 @@ def refine_vjp_host(R, t, status, grad_R=None, grad_t=None, pts_2d=None, line_2d
     result always holds ``vjp_status`` and ``info``.  The output arrays are filled with NaN before the call: every element the library
     owes is written by it."""
     want, admit_mask = _chk_want(want), _chk_admit(admit_mask)
-    Rn = _np64(R)
-    if Rn.ndim != 3 or Rn.shape[1:] != (3, 3):
-        raise ValueError("R: expected [B,3,3]")
-    B = Rn.shape[0]
-    tn = _np64(t)
-    if tn.shape != (B, 3):
-        raise ValueError(f"t: expected [{B},3]")
-    gR, gt = _np64(grad_R), _np64(grad_t)
-    if gR is not None and gR.shape != (B, 3, 3):
-        raise ValueError(f"grad_R: expected [{B},3,3]")
-    if gt is not None and gt.shape != (B, 3):
-        raise ValueError(f"grad_t: expected [{B},3]")
-    p2, p3, l2, l3 = _np64(pts_2d), _np64(pts_3d), _np64(line_2d), _np64(line_3d)
-    n_p = p3.shape[1] if p3 is not None and p3.ndim == 3 else 0
-    n_l = l3.shape[1] if l3 is not None and l3.ndim == 4 else 0
-    if n_p == 0 and n_l == 0:
-        raise ValueError("need at least one point or line correspondence")
-    if n_p and (p3.shape != (B, n_p, 3) or p2 is None or p2.shape != (B, n_p, 2)):
-        raise ValueError("points: expected pts_2d [B,n_p,2] and pts_3d [B,n_p,3]")
-    if n_l and (l3.shape != (B, n_l, 2, 3) or l2 is None or l2.shape != (B, n_l, 2, 2)):
-        raise ValueError("lines: expected line_2d [B,n_l,2,2] and line_3d [B,n_l,2,3]")
-    Kn = _np64(K)
-    if Kn is None or Kn.shape not in ((3, 3), (B, 3, 3)):
-        raise ValueError(f"K must be [3,3] or [{B},3,3]")
-    st = np.ascontiguousarray(status, dtype=np.int32) if status is not None else None
-    if st is not None and st.shape != (B,):
-        raise ValueError(f"status: expected [{B}]")
-    mp = np.ascontiguousarray(mask_pts, dtype=np.uint8) if mask_pts is not None and n_p else None
-    ml = np.ascontiguousarray(mask_lines, dtype=np.uint8) if mask_lines is not None and n_l else None
-    if mp is not None and mp.shape != (B, n_p):
-        raise ValueError(f"mask_pts: expected [{B},{n_p}]")
-    if ml is not None and ml.shape != (B, n_l):
-        raise ValueError(f"mask_lines: expected [{B},{n_l}]")
-    out = {"pts_2d": np.full((B, n_p, 2), np.nan) if n_p and "pts_2d" in want else None,
-           "pts_3d": np.full((B, n_p, 3), np.nan) if n_p and "pts_3d" in want else None,
-           "line_2d": np.full((B, n_l, 2, 2), np.nan) if n_l and "line_2d" in want else None,
-           "line_3d": np.full((B, n_l, 2, 3), np.nan) if n_l and "line_3d" in want else None,
-           "vjp_status": np.full(B, -1, np.int32), "info": np.full((B, 2), np.nan)}
+    a = host_args(R, t, pts_2d, line_2d, pts_3d, line_3d, K, status, mask_pts, mask_lines, grad_R=grad_R, grad_t=grad_t)
+    B = a.B
+    out = grad_outputs(want, (B, a.n_p), (B, a.n_l), lambda shape: np.full(shape, np.nan))
+    out.update(vjp_status=np.full(B, -1, np.int32), info=np.full((B, 2), np.nan))
     L = _lib.refine_grad_lib()
-    rc = L.cvxpnpl_refine_vjp_batch_host(B, n_p, _cp(p2), _cp(p3), n_l, _cp(l2), _cp(l3), _cp(Kn), int(Kn.ndim == 3), _cp(Rn), _cp(tn), _cp(st), 1,
-                                         admit_mask, _cp(mp), _cp(ml), _cp(gR), _cp(gt), _cp(out["pts_2d"]), _cp(out["pts_3d"]), _cp(out["line_2d"]),
-                                         _cp(out["line_3d"]), _cp(out["vjp_status"]), _cp(out["info"]), int(n_threads))
+    rc = L.cvxpnpl_refine_vjp_batch_host(B, a.n_p, _cp(a.p2), _cp(a.p3), a.n_l, _cp(a.l2), _cp(a.l3), _cp(a.K), int(a.K.ndim == 3), _cp(a.R), _cp(a.t),
+                                         _cp(a.st), 1, admit_mask, _cp(a.mp), _cp(a.ml), _cp(a.gR), _cp(a.gt), _cp(out["pts_2d"]), _cp(out["pts_3d"]),
+                                         _cp(out["line_2d"]), _cp(out["line_3d"]), _cp(out["vjp_status"]), _cp(out["info"]), int(n_threads))
     if rc != 0:
         raise ValueError(f"cvxpnpl_refine_vjp_batch_host failed ({rc}): {L.cvxpnpl_refine_grad_last_error().decode()}")
     return out

@@ -22,8 +22,9 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._refine_args import _cp, batch_args, host_args, scene_args
 from .api import _ptr, _require_gpu
-from .refine import ADMIT_USABLE, _chk, _chk_status, _cp, _np64, _pair
+from .refine import ADMIT_USABLE
 
 __all__ = ["RobustRefineResult", "refine_pose_batch_robust", "refine_scenes_robust", "refine_pose_batch_robust_host", "LOSSES"]
 
@@ -78,38 +79,16 @@ def refine_pose_batch_robust(R, t, pts_2d=None, line_2d=None, pts_3d=None, line_
     admits gives status 4.  Returns a RobustRefineResult of device tensors; nothing is synchronised.  Statuses and pass-through as
     ``refine_pose_batch``; robust_w [B, n_p + n_l] (points then lines)."""
     o = _opts(loss, scale_px, max_iters, step_tol)
-    if not isinstance(R, torch.Tensor) or R.dim() != 3:
-        raise ValueError("R: expected a torch tensor [B,3,3]")
-    B, dev = int(R.shape[0]), R.device
-    _chk(R, "R", torch.float64, (B, 3, 3), dev)
-    _chk(t, "t", torch.float64, (B, 3), dev)
-    p2, p3, n_p = _pair(pts_2d, pts_3d, "points", (2,), (3,), dev, B)
-    l2, l3, n_l = _pair(line_2d, line_3d, "lines", (2, 2), (2, 3), dev, B)
-    if n_p == 0 and n_l == 0:
-        raise ValueError("need at least one point or line correspondence")
-    if not isinstance(K, torch.Tensor) or tuple(K.shape) not in ((3, 3), (B, 3, 3)):
-        raise ValueError(f"K must be a tensor [3,3] or [{B},3,3]")
-    per = int(K.dim() == 3)
-    _chk(K, "K", torch.float64, (B, 3, 3) if per else (3, 3), dev)
-    st, stride = _chk_status(status, B, dev)
-    if mask_pts is not None:
-        _chk(mask_pts, "mask_pts", torch.uint8, (B, n_p), dev)
-    if mask_lines is not None:
-        _chk(mask_lines, "mask_lines", torch.uint8, (B, n_l), dev)
-    if weights_pts is not None:
-        _chk(weights_pts, "weights_pts", torch.float64, (B, n_p), dev)
-    if weights_lines is not None:
-        _chk(weights_lines, "weights_lines", torch.float64, (B, n_l), dev)
-    if dev.type != "cuda":
-        raise ValueError(f"the poses are on {dev}: cvxpnpl_amd has no CPU path (refine_pose_batch_robust_host is the host form)")
+    a = batch_args("refine_pose_batch_robust_host", R, t, pts_2d, line_2d, pts_3d, line_3d, K, status, mask_pts, mask_lines, weights_pts, weights_lines)
     _require_gpu()
     L = _lib.refine_robust_lib()
+    B, dev = a.B, a.dev
     oR, ot, cost, iters, ost, n_live, n_in = _outputs(B, dev)
-    rw = torch.empty((B, n_p + n_l), dtype=torch.float64, device=dev)
+    rw = torch.empty((B, a.n_p + a.n_l), dtype=torch.float64, device=dev)
     with torch.cuda.device(dev):
-        rc = L.cvxpnpl_refine_robust_batch(B, n_p, _ptr(p2), _ptr(p3), n_l, _ptr(l2), _ptr(l3), _ptr(K), per, _ptr(R), _ptr(t), _ptr(st), stride,
-                                           int(admit_mask), _ptr(mask_pts), _ptr(mask_lines), _ptr(weights_pts), _ptr(weights_lines), C.byref(o),
-                                           _ptr(oR), _ptr(ot), _ptr(cost), _ptr(iters), _ptr(ost), _ptr(n_live), _ptr(rw), _ptr(n_in),
+        rc = L.cvxpnpl_refine_robust_batch(B, a.n_p, _ptr(a.p2), _ptr(a.p3), a.n_l, _ptr(a.l2), _ptr(a.l3), _ptr(K), a.per, _ptr(R), _ptr(t), _ptr(a.st),
+                                           a.stride, int(admit_mask), _ptr(mask_pts), _ptr(mask_lines), _ptr(weights_pts), _ptr(weights_lines),
+                                           C.byref(o), _ptr(oR), _ptr(ot), _ptr(cost), _ptr(iters), _ptr(ost), _ptr(n_live), _ptr(rw), _ptr(n_in),
                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise RuntimeError(f"cvxpnpl_refine_robust_batch failed ({rc}): {L.cvxpnpl_refine_robust_last_error().decode()}")
@@ -122,55 +101,24 @@ def refine_scenes_robust(sc, R, t, loss: str = "huber", scale_px: float = 1.0, w
     weights_pts [sum P] / weights_lines [sum L] float64 and mask_pts / mask_lines uint8, all optional; status [F] int32 (optional, may be
     ``head[:, 0]`` of the RANSAC read-back).  The use it is made for: a RANSAC pose polished over ALL records of its scene, no mask,
     ``scale_px`` the RANSAC threshold.  One workgroup per scene, no synchronisation.  robust_w is the pair ([sum P], [sum L] or None)."""
-    from . import ransac as _rn
-
     o = _opts(loss, scale_px, max_iters, step_tol)
-    lines = isinstance(sc, _rn.PnplScenes)
-    if not lines and not isinstance(sc, _rn.Scenes):
-        raise ValueError("sc: expected ransac.Scenes or ransac.PnplScenes")
-    (_rn._chk_pnpl_scenes if lines else _rn._chk_scenes)(sc)
-    F, dev = sc.F, sc.device
-    _chk(R, "R", torch.float64, (F, 3, 3), dev)
-    _chk(t, "t", torch.float64, (F, 3), dev)
-    st, stride = _chk_status(status, F, dev)
-    n_lines = sc.line_total if lines else 0
-    if mask_pts is not None:
-        _chk(mask_pts, "mask_pts", torch.uint8, (sc.total,), dev)
-    if weights_pts is not None:
-        _chk(weights_pts, "weights_pts", torch.float64, (sc.total,), dev)
-    if (mask_lines is not None or weights_lines is not None) and not lines:
-        raise ValueError("mask_lines / weights_lines given for scenes without lines")
-    if mask_lines is not None:
-        _chk(mask_lines, "mask_lines", torch.uint8, (n_lines,), dev)
-    if weights_lines is not None:
-        _chk(weights_lines, "weights_lines", torch.float64, (n_lines,), dev)
+    a = scene_args(sc, R, t, status, mask_pts, mask_lines, weights=(weights_pts, weights_lines))
     _require_gpu()
     L = _lib.refine_robust_lib()
+    F, dev = a.F, a.dev
     oR, ot, cost, iters, ost, n_live, n_in = _outputs(F, dev)
     # (zeros: a record outside every scene's slice is written by no workgroup)
-    rw_p = torch.zeros((sc.total,), dtype=torch.float64, device=dev)
-    rw_l = torch.zeros((n_lines,), dtype=torch.float64, device=dev) if lines else None
+    rw_p = torch.zeros((a.n_pts,), dtype=torch.float64, device=dev)
+    rw_l = torch.zeros((a.n_lines,), dtype=torch.float64, device=dev) if a.off_l is not None else None
     with torch.cuda.device(dev):
-        rc = L.cvxpnpl_refine_robust_scenes(F, _ptr(sc.offsets), sc.total, _ptr(sc.line_offsets) if lines else None, n_lines, _ptr(sc.x), _ptr(sc.X),
-                                            _ptr(sc.l2) if lines else None, _ptr(sc.l3) if lines else None, _ptr(sc.K), sc.per_scene_K, _ptr(R), _ptr(t),
-                                            _ptr(st), stride, int(admit_mask), _ptr(mask_pts), _ptr(mask_lines), _ptr(weights_pts), _ptr(weights_lines),
-                                            C.byref(o), _ptr(oR), _ptr(ot), _ptr(cost), _ptr(iters), _ptr(ost), _ptr(n_live), _ptr(rw_p), _ptr(rw_l),
-                                            _ptr(n_in), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = L.cvxpnpl_refine_robust_scenes(F, _ptr(sc.offsets), a.n_pts, _ptr(a.off_l), a.n_lines, _ptr(sc.x), _ptr(sc.X), _ptr(a.l2), _ptr(a.l3),
+                                            _ptr(sc.K), sc.per_scene_K, _ptr(R), _ptr(t), _ptr(a.st), a.stride, int(admit_mask), _ptr(mask_pts),
+                                            _ptr(mask_lines), _ptr(weights_pts), _ptr(weights_lines), C.byref(o), _ptr(oR), _ptr(ot), _ptr(cost),
+                                            _ptr(iters), _ptr(ost), _ptr(n_live), _ptr(rw_p), _ptr(rw_l), _ptr(n_in),
+                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
     if rc != 0:
         raise RuntimeError(f"cvxpnpl_refine_robust_scenes failed ({rc}): {L.cvxpnpl_refine_robust_last_error().decode()}")
     return RobustRefineResult(oR, ot, cost, iters, ost, n_live, (rw_p, rw_l), n_in)
-
-
-def _weights_np(w, name, shape):
-    if w is None:
-        return None
-    if not isinstance(w, np.ndarray) or w.dtype != np.float64:
-        raise ValueError(f"{name}: expected a float64 numpy array")
-    if w.shape != shape:
-        raise ValueError(f"{name}: shape {w.shape}, expected {shape}")
-    if not w.flags.c_contiguous:
-        raise ValueError(f"{name}: not contiguous")
-    return w
 
 
 def refine_pose_batch_robust_host(R, t, pts_2d=None, line_2d=None, pts_3d=None, line_3d=None, K=None, loss: str = "huber", scale_px: float = 1.0,
@@ -179,43 +127,15 @@ def refine_pose_batch_robust_host(R, t, pts_2d=None, line_2d=None, pts_3d=None, 
     """``refine_pose_batch_robust`` on host threads (``cvxpnpl_refine_robust_batch_host``, the same source as the kernels): numpy arrays in
     and out; the weights are float64 arrays of the exact shape."""
     o = _opts(loss, scale_px, max_iters, step_tol)
-    Rn = _np64(R)
-    if Rn.ndim != 3 or Rn.shape[1:] != (3, 3):
-        raise ValueError("R: expected [B,3,3]")
-    B = Rn.shape[0]
-    tn = _np64(t)
-    if tn.shape != (B, 3):
-        raise ValueError(f"t: expected [{B},3]")
-    p2, p3, l2, l3 = _np64(pts_2d), _np64(pts_3d), _np64(line_2d), _np64(line_3d)
-    n_p = p3.shape[1] if p3 is not None and p3.ndim == 3 else 0
-    n_l = l3.shape[1] if l3 is not None and l3.ndim == 4 else 0
-    if n_p == 0 and n_l == 0:
-        raise ValueError("need at least one point or line correspondence")
-    if n_p and (p3.shape != (B, n_p, 3) or p2 is None or p2.shape != (B, n_p, 2)):
-        raise ValueError("points: expected pts_2d [B,n_p,2] and pts_3d [B,n_p,3]")
-    if n_l and (l3.shape != (B, n_l, 2, 3) or l2 is None or l2.shape != (B, n_l, 2, 2)):
-        raise ValueError("lines: expected line_2d [B,n_l,2,2] and line_3d [B,n_l,2,3]")
-    Kn = _np64(K)
-    if Kn is None or Kn.shape not in ((3, 3), (B, 3, 3)):
-        raise ValueError(f"K must be [3,3] or [{B},3,3]")
-    st = np.ascontiguousarray(status, dtype=np.int32) if status is not None else None
-    if st is not None and st.shape != (B,):
-        raise ValueError(f"status: expected [{B}]")
-    mp = np.ascontiguousarray(mask_pts, dtype=np.uint8) if mask_pts is not None and n_p else None
-    ml = np.ascontiguousarray(mask_lines, dtype=np.uint8) if mask_lines is not None and n_l else None
-    if mp is not None and mp.shape != (B, n_p):
-        raise ValueError(f"mask_pts: expected [{B},{n_p}]")
-    if ml is not None and ml.shape != (B, n_l):
-        raise ValueError(f"mask_lines: expected [{B},{n_l}]")
-    wp = _weights_np(weights_pts, "weights_pts", (B, n_p))
-    wl = _weights_np(weights_lines, "weights_lines", (B, n_l))
+    a = host_args(R, t, pts_2d, line_2d, pts_3d, line_3d, K, status, mask_pts, mask_lines, weights_pts, weights_lines)
+    B = a.B
     oR, ot, cost = np.empty((B, 3, 3)), np.empty((B, 3)), np.empty((B, 2))
     iters, ost, n_live, n_in = np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.int32), np.empty(B, np.int32)
-    rw = np.empty((B, n_p + n_l))
+    rw = np.empty((B, a.n_p + a.n_l))
     L = _lib.refine_robust_lib()
-    rc = L.cvxpnpl_refine_robust_batch_host(B, n_p, _cp(p2), _cp(p3), n_l, _cp(l2), _cp(l3), _cp(Kn), int(Kn.ndim == 3), _cp(Rn), _cp(tn), _cp(st), 1,
-                                            int(admit_mask), _cp(mp), _cp(ml), _cp(wp), _cp(wl), C.byref(o), _cp(oR), _cp(ot), _cp(cost), _cp(iters),
-                                            _cp(ost), _cp(n_live), _cp(rw), _cp(n_in), int(n_threads))
+    rc = L.cvxpnpl_refine_robust_batch_host(B, a.n_p, _cp(a.p2), _cp(a.p3), a.n_l, _cp(a.l2), _cp(a.l3), _cp(a.K), int(a.K.ndim == 3), _cp(a.R), _cp(a.t),
+                                            _cp(a.st), 1, int(admit_mask), _cp(a.mp), _cp(a.ml), _cp(a.wp), _cp(a.wl), C.byref(o), _cp(oR), _cp(ot),
+                                            _cp(cost), _cp(iters), _cp(ost), _cp(n_live), _cp(rw), _cp(n_in), int(n_threads))
     if rc != 0:
         raise ValueError(f"cvxpnpl_refine_robust_batch_host failed ({rc}): {L.cvxpnpl_refine_robust_last_error().decode()}")
     return RobustRefineResult(oR, ot, cost, iters, ost, n_live, rw, n_in)
