@@ -426,6 +426,35 @@ def ransac_guided_lib():
     return L
 
 
+# adaptive and guided RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl_adaptive.h): the eleventh library
+RANSAC_PNPL_ADAPTIVE_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_pnpl_adaptive.so")
+RANSAC_PNPL_ADAPTIVE_EXPORTS = ("cvxpnpl_ransac_pnpl_adaptive_sample_assemble", "cvxpnpl_ransac_pnpl_adaptive_score",
+                                "cvxpnpl_ransac_pnpl_adaptive_update", "cvxpnpl_ransac_pnpl_adaptive_last_error")
+
+_ransac_pnpl_adaptive_lib = None
+
+
+def ransac_pnpl_adaptive_lib():
+    """Load libcvxpnpl_amd_ransac_pnpl_adaptive.so (loudly)."""
+    global _ransac_pnpl_adaptive_lib
+    if _ransac_pnpl_adaptive_lib is not None:
+        return _ransac_pnpl_adaptive_lib
+    if not os.path.exists(RANSAC_PNPL_ADAPTIVE_LIB_PATH):
+        raise LibraryMissing(f"{RANSAC_PNPL_ADAPTIVE_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(RANSAC_PNPL_ADAPTIVE_LIB_PATH)
+    p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
+    scenes = [p, i64, p, i64]  # d_pt_offsets, n_pts, d_ln_offsets, n_lines
+    L.cvxpnpl_ransac_pnpl_adaptive_sample_assemble.argtypes = [i64, i64, p, i32, i32, i32, i32] + scenes + [p, p, p, p, p, p, p, i32, p, p, p, p]
+    L.cvxpnpl_ransac_pnpl_adaptive_score.argtypes = [i64, i64, p, i32] + scenes + [p, p, p, C.c_uint32, p, i32, p, p, p, p, C.c_double, p, p]
+    L.cvxpnpl_ransac_pnpl_adaptive_update.argtypes = [i64, i64, p, i32, i32, i32, C.c_double] + scenes + [p, p, p, p, p, i32, p, p, p, p, C.c_double,
+                                                                                                            p, p, p, p, p, p, p, p, p]
+    for name in RANSAC_PNPL_ADAPTIVE_EXPORTS[:-1]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_ransac_pnpl_adaptive_last_error.restype = C.c_char_p
+    _ransac_pnpl_adaptive_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -67,7 +67,8 @@ def ransac_compile_cmd(out=RANSAC_OUT):
 RANSAC_PNPL_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_hip.hip")
 RANSAC_PNPL_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.so")
 RANSAC_PNPL_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.resources.txt")
-RANSAC_PNPL_DEPS = [RANSAC_PNPL_SRC, os.path.join(HERE, "csrc", "ransac_pnpl_kernel.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+RANSAC_PNPL_DEPS = [RANSAC_PNPL_SRC, os.path.join(HERE, "csrc", "ransac_pnpl_kernel.h"), os.path.join(HERE, "csrc", "ransac_pnpl_common.h"),
+                    os.path.join(HERE, "csrc", "ransac_common.h"),
                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                     os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_pnpl.h")]
 
@@ -168,6 +169,22 @@ def ransac_guided_compile_cmd(out=RANSAC_GUIDED_OUT):
     return ransac_compile_cmd(out)[:-1] + [RANSAC_GUIDED_SRC]
 
 
+# adaptive and guided RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl_adaptive.h): the eleventh library, the flags of the
+# third
+RANSAC_PNPL_ADAPTIVE_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_adaptive_hip.hip")
+RANSAC_PNPL_ADAPTIVE_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_adaptive.so")
+RANSAC_PNPL_ADAPTIVE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_adaptive.resources.txt")
+RANSAC_PNPL_ADAPTIVE_DEPS = [RANSAC_PNPL_ADAPTIVE_SRC, os.path.join(HERE, "csrc", "ransac_pnpl_adaptive_kernel.h"),
+                             os.path.join(HERE, "csrc", "ransac_pnpl_common.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
+                             os.path.join(HERE, "csrc", "ransac_guided_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                             os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                             os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_pnpl_adaptive.h")]
+
+
+def ransac_pnpl_adaptive_compile_cmd(out=RANSAC_PNPL_ADAPTIVE_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_PNPL_ADAPTIVE_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -222,8 +239,12 @@ def build_ransac_guided(force=False, verbose=False):
     return _build_one(RANSAC_GUIDED_OUT, RANSAC_GUIDED_RESOURCES, RANSAC_GUIDED_DEPS, ransac_guided_compile_cmd(), force, verbose)
 
 
+def build_ransac_pnpl_adaptive(force=False, verbose=False):
+    return _build_one(RANSAC_PNPL_ADAPTIVE_OUT, RANSAC_PNPL_ADAPTIVE_RESOURCES, RANSAC_PNPL_ADAPTIVE_DEPS, ransac_pnpl_adaptive_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All ten libraries; returns the solver's (OUT)."""
+    """All eleven libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -234,6 +255,7 @@ def build(force=False, verbose=False):
     build_refine_robust_grad(force, verbose)
     build_ransac_adaptive(force, verbose)
     build_ransac_guided(force, verbose)
+    build_ransac_pnpl_adaptive(force, verbose)
     return OUT
 
 

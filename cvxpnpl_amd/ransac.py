@@ -1002,8 +1002,178 @@ def solve_minimal_costs(Q45, B27, eps: float = 1e-6, max_iters: int = 100, devic
     return solve_cost_batch(Q45, B27, eps=eps, max_iters=max_iters, device=device, **{**MINIMAL_SOLVER_OPTS, **solver_opts})
 
 
+# ---- points AND lines with a budget per scene and ranked draws (include/cvxpnpl_amd_ransac_pnpl_adaptive.h) --------
+# ransac_pnpl_batch(confidence=..., quality=..., line_quality=...): the rounds of section 19 and the ranked draws of section 20 over the
+# UNION of a scene's points and lines (index c < P_f: point c; otherwise line c - P_f; M_f = P_f + L_f).  The start of a call, the
+# compaction and the ranking are the ninth and tenth libraries', which know nothing of what a correspondence is; the three kernels that
+# touch points and lines are those of libcvxpnpl_amd_ransac_pnpl_adaptive.so.  The stage wrappers below check every tensor as _chk does.
+
+
+def _call_pnpl_adaptive(sc: PnplScenes, name, *args):
+    with torch.cuda.device(sc.device):
+        L = _lib.ransac_pnpl_adaptive_lib()
+        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_pnpl_adaptive_last_error().decode()}")
+
+
+def adaptive_pnpl_init(sc: PnplScenes) -> AdaptiveState:
+    """adaptive_init for scenes of points and lines: the state of section 19 (cvxpnpl_ransac_adaptive_init, which reads nothing of a
+    scene), its mask the POINT mask [sum P], and beside it mask_lines [sum L] uint8."""
+    _chk_pnpl_scenes(sc)
+    st = adaptive_init(sc)
+    st.mask_lines = torch.empty((sc.line_total,), dtype=torch.uint8, device=sc.device)
+    return st
+
+
+def rank_pnpl_scenes(sc: PnplScenes, quality, line_quality):
+    """The ranking of a guided call: order [sum P + sum L] int32, scene f's slice -- from offsets[f] + line_offsets[f] on -- the union
+    indices of its correspondences, best first, by cvxpnpl_ransac_guided_rank (rank_scenes) over the union offsets and the union-packed
+    quality (per scene: points, then lines).  quality [sum P], line_quality [sum L]: float64 on the scenes' device, on ONE scale; either
+    may be None where the scene set has no such correspondence.  No synchronisation."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    dev, n = sc.device, sc.total + sc.line_total
+    union = torch.empty((n,), dtype=torch.float64, device=dev)
+    off_p, off_l = _np.concatenate([[0], _np.cumsum(sc.sizes)]), _np.concatenate([[0], _np.cumsum(sc.line_sizes)])
+    if sc.total:  # point m of scene f sits at its packed place plus the lines of the scenes before it ...
+        _chk(quality, "quality", torch.float64, (sc.total,), dev)
+        union[torch.as_tensor(_np.arange(sc.total) + _np.repeat(off_l[:-1], sc.sizes)).to(dev)] = quality
+    if sc.line_total:  # ... and line m at its packed place plus the points of the scenes up to its own
+        _chk(line_quality, "line_quality", torch.float64, (sc.line_total,), dev)
+        union[torch.as_tensor(_np.arange(sc.line_total) + _np.repeat(off_p[1:], sc.line_sizes)).to(dev)] = line_quality
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    _call_guided(sc, "cvxpnpl_ransac_guided_rank", sc.F, _ptr((sc.offsets + sc.line_offsets).contiguous()), n,
+                 max(p + l for p, l in zip(sc.sizes, sc.line_sizes)), _ptr(union), _ptr(order))
+    return order
+
+
+def sample_assemble_active(sc: PnplScenes, active, n_active: int, hyp0: int, n_round: int, cap: int, order=None, pool_full: int = 0, seeds=None,
+                           want_idx: bool = False):
+    """cvxpnpl_ransac_pnpl_adaptive_sample_assemble: for entry a < n_active of `active`, the hypotheses hyp0 .. hyp0 + n_round - 1 of scene
+    active[a], drawn and assembled as sample_assemble_scenes does -- without order (or with pool_full = 0) the rows
+    [f, hyp0 : hyp0 + n_round] of sample_assemble_scenes(sc, hyp0 + n_round), bit for bit.  order (rank_pnpl_scenes) with pool_full > 0:
+    hypothesis h of the scene draws from the pool_size(h, P_f + L_f, pool_full) best-ranked correspondences of the union while
+    h < pool_full.  Returns (Q45 [A*n_round,45], B27 [A*n_round,27]) and, with want_idx, idx [A*n_round,4] int32 (union indices).  An
+    entry of active outside [0, F) leaves its rows unwritten; an order entry outside [0, M_f) gives the NaN cost with idx = -1."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    A, dev, pf = _chk_active(sc, active, n_active), sc.device, _chk_pool_full(pool_full)
+    h0, Hr, cp = _chk_budget(hyp0, n_round, cap)
+    if order is None:
+        if pf > 0:
+            raise ValueError("pool_full > 0 needs order (rank_pnpl_scenes)")
+    else:
+        _chk(order, "order", torch.int32, (sc.total + sc.line_total,), dev)
+    if seeds is None:
+        if sc.seeds is None:
+            raise ValueError("no seeds: give them here or to pack_pnpl_scenes")
+        sd = sc.seeds
+    else:
+        if len(seeds) != sc.F:
+            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
+        sd = torch.as_tensor(_seed_words(seeds)).to(dev)
+    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
+    n = A * Hr
+    Qt = torch.empty((n, 45), dtype=torch.float64, device=dev)
+    Bt = torch.empty((n, 27), dtype=torch.float64, device=dev)
+    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
+    _call_pnpl_adaptive(sc, "cvxpnpl_ransac_pnpl_adaptive_sample_assemble", sc.F, A, _ptr(active), h0, Hr, cp, pf, *_scene_args(sc), _ptr(sd), _ptr(order),
+                        *_data_args(sc), _ptr(sc.K), sc.per_scene_K, _ptr(idx), _ptr(Qt), _ptr(Bt))
+    return (Qt, Bt, idx) if want_idx else (Qt, Bt)
+
+
+def score_pnpl_active(sc: PnplScenes, active, n_active: int, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
+    """cvxpnpl_ransac_pnpl_adaptive_score: count [A*n_round] int32, the point plus line inliers of (R, t)[a*n_round + h] in scene
+    active[a]; predicates and status rule of score_pnpl_scenes."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    A = _chk_active(sc, active, n_active)
+    Hr = _chk_round(sc, A, R, t, status)
+    count = torch.empty((A * Hr,), dtype=torch.int32, device=sc.device)
+    _call_pnpl_adaptive(sc, "cvxpnpl_ransac_pnpl_adaptive_score", sc.F, A, _ptr(active), Hr, *_scene_args(sc), _ptr(R), _ptr(t), _ptr(status),
+                        _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(count))
+    return count
+
+
+def update_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, hyp0: int, cap: int, confidence: float, count, R, t, status,
+                       thresh: float = 2.0):
+    """cvxpnpl_ransac_pnpl_adaptive_update on the first n_active entries of st.active (a state of adaptive_pnpl_init): update_active with
+    two masks -- st.mask (points) and st.mask_lines change together with pose, head and best -- and the stopping rule on P_f + L_f.
+    n_round is R.shape[0] / n_active.  In place, no synchronisation; compact_active(sc, st, n_active) follows."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    _chk_state(sc, st)
+    _chk(getattr(st, "mask_lines", None), "state.mask_lines", torch.uint8, (sc.line_total,), sc.device)
+    conf, _ = _check_adaptive(confidence, 1)
+    A = _chk_active(sc, st.active, n_active)
+    if status is None:
+        raise ValueError("status is required")
+    Hr = _chk_round(sc, A, R, t, status, count)
+    h0, Hr, cp = _chk_budget(hyp0, Hr, cap)
+    _call_pnpl_adaptive(sc, "cvxpnpl_ransac_pnpl_adaptive_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, *_scene_args(sc), _ptr(count), _ptr(R),
+                        _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+                        _ptr(st.best), _ptr(st.mask), _ptr(st.mask_lines), _ptr(st.hyp_used), _ptr(st.done))
+
+
+def _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, packed_p, packed_l, n_hyp):
+    """Host-side validation of the guided keywords of ransac_pnpl_batch (nothing here needs a GPU): returns pool_full (None for an
+    unguided call; n_hyp by default).  A guided call gives a quality for every kind of correspondence the scene set holds."""
+    if quality is None and line_quality is None:
+        if pool_full is not None:
+            raise ValueError("pool_full given without quality")
+        return None
+    for q, szs, what, other in ((quality, ps, "quality", "points"), (line_quality, ls, "line_quality", "lines")):
+        if q is None and sum(szs):
+            raise ValueError(f"a guided call ranks points and lines together: the scenes hold {other}, {what} is missing")
+        if q is not None and not sum(szs):
+            raise ValueError(f"{what} given, the scenes hold no {other}")
+    pf = int(n_hyp) if pool_full is None else _chk_pool_full(pool_full)
+    for q, szs, packed, what in ((quality, ps, packed_p, "quality"), (line_quality, ls, packed_l, "line_quality")):
+        if q is None:
+            continue
+        if not packed and isinstance(q, (list, tuple)):  # a scene without this kind may give None
+            q = [_np.zeros(0) if a is None else a for a in q]
+        try:
+            _check_quality(q, 0, szs, packed, n_hyp)
+        except ValueError as e:
+            raise ValueError(str(e).replace("quality", what)) from None
+    return pf
+
+
+def _pack_quality(q, packed, device):
+    """One kind's quality as float64 [n] on the device (None stays None)."""
+    if q is None:
+        return None
+    if isinstance(q, (list, tuple)):
+        q = _np.asarray(q, dtype=_np.float64) if packed else [a for a in q if a is not None and _numel(a) > 0]
+    return _to_dev(q, device).reshape(-1)
+
+
+def _adaptive_pnpl_rounds(sc, cap, conf, round_hyp, thresh, eps, max_iters, solver_opts, guided=None):
+    """The rounds of ransac_pnpl_batch(confidence=...): _adaptive_rounds with the minimal solves at the cost seam.  Returns the state and
+    the number of rounds; one 4-byte read-back per round.  guided: (order, pool_full)."""
+    st = adaptive_pnpl_init(sc)
+    order, pf = guided if guided is not None else (None, 0)
+    A, h0, rounds = sc.F, 0, 0
+    while A > 0 and h0 < cap:
+        Hr = min(round_hyp, cap - h0)
+        Qh, Bh = sample_assemble_active(sc, st.active, A, h0, Hr, cap, order, pf)
+        res = solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+        count = score_pnpl_active(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+        update_pnpl_active(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
+        compact_active(sc, st, A)
+        A = int(st.n_active.cpu()[0])   # the round's one synchronisation
+        st.swap()
+        h0 += Hr
+        rounds += 1
+    return st, rounds
+
+
 def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0,
-                      refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, polish: bool = False, **solver_opts):
+                      refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, polish: bool = False,
+                      confidence: Optional[float] = None, round_hyp: int = 64, quality=None, line_quality=None, pool_full: Optional[int] = None,
+                      **solver_opts):
     """Robust PnPL for F scenes of different sizes in one launch sequence; the argument order is pnpl's.
 
     Scenes: lists of F arrays pts_2d[f] [P_f,2] / pts_3d[f] [P_f,3] / line_2d[f] [L_f,2,2] / line_3d[f] [L_f,2,3], or packed arrays with
@@ -1014,9 +1184,25 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
     Returns a dict: R [F,3,3], t [F,3], inliers_pts (packed bool [sum P]) with offsets [F+1], inliers_lines (packed bool [sum L]) with
     line_offsets [F+1] on the device; n_inliers (points + lines, a line counting once), status, n_certified, best_index [F] (host, columns
     of the one read-back `head` [F,4]); sizes, line_sizes, n_hyp.  One host synchronisation per call.
-    polish=True: as in ransac_pnp_batch, over both consensus masks; the result gains "refine"."""
+    polish=True: as in ransac_pnp_batch, over both consensus masks; the result gains "refine".
+    confidence (0 < confidence < 1; None: the fixed budget above, unchanged), round_hyp: as in ransac_pnp_batch, on the UNION of a scene's
+    correspondences -- n_hyp becomes the CAP per scene, the hypotheses are drawn, assembled, solved and scored in rounds of round_hyp for
+    the scenes still active, and scene f stops once it has drawn N(best, P_f + L_f, confidence) hypotheses (needed_hypotheses), best its
+    highest inlier count so far (points plus lines), or n_hyp.  A scene that stops after u hypotheses holds what the fixed budget
+    n_hyp = u selects; refits and polish then run over all scenes.  The result gains hyp_used [F] (host int32), rounds and confidence.
+    One 4-byte read-back per round on top of the call's own.
+    quality / line_quality (None: uniform draws, the code above unchanged): a matcher's score per point / per line, higher is better --
+    lists of F arrays [P_f] / [L_f] (None for a scene without that kind), or packed [sum P] / [sum L] with `sizes` / `line_sizes`; any
+    real dtype.  A guided call gives one for every kind of correspondence the scenes hold.  The two are compared ON ONE SCALE: points and
+    lines are ranked together, and making a point score comparable with a line score is the caller's contract.  Every scene's union is
+    ranked once (rank_pnpl_scenes) and hypothesis h draws its minimal set from the pool_size(h, P_f + L_f, pool_full) best-ranked
+    correspondences while h < pool_full; from there on the draws are the uniform ones.  pool_full (an int >= 0) defaults to n_hyp; 0 is
+    the uniform sampler bit for bit.  With confidence the stopping rule is unchanged and counts inliers of the whole scene.  The result
+    gains pool_full."""
     ps, ls = _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes)
     F = len(ps)
+    if confidence is not None:
+        conf, round_hyp = _check_adaptive(confidence, round_hyp)
     if seed is None:
         seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
     if isinstance(seed, (int, _np.integer)):
@@ -1027,12 +1213,24 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
             raise ValueError(f"{len(seeds)} seeds for {F} scenes")
     if int(n_hyp) < 1:
         raise ValueError("n_hyp must be at least 1")
+    pool_full = _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, sizes is not None, line_sizes is not None, n_hyp)
     sc = pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=sizes, line_sizes=line_sizes, device=device, seeds=seeds)
-    # no torch kernel from here to the read-back: draw + minimal assembly, the F * n_hyp minimal solves at the cost seam ...
-    Qh, Bh = sample_assemble_scenes(sc, n_hyp)
-    res = solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
-    count = score_pnpl_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
-    R, t, head, mp, ml = select_pnpl_scenes(sc, count, res.R, res.t, res.status, thresh)
+    guided = None
+    if pool_full is not None:  # the ranking of every scene's union: once per call, before the launch sequence
+        guided = (rank_pnpl_scenes(sc, _pack_quality(quality, sizes is not None, sc.device), _pack_quality(line_quality, line_sizes is not None, sc.device)),
+                  pool_full)
+    if confidence is not None:
+        state, rounds = _adaptive_pnpl_rounds(sc, int(n_hyp), conf, round_hyp, thresh, eps, max_iters, solver_opts, guided)
+        R, t, head, mp, ml = state.R, state.t, state.head, state.mask, state.mask_lines
+    else:
+        # no torch kernel from here to the read-back: draw + minimal assembly, the F * n_hyp minimal solves at the cost seam ...
+        if guided is None:
+            Qh, Bh = sample_assemble_scenes(sc, n_hyp)
+        else:  # the round sampler over the identity active list: problem f * n_hyp + h, the fixed layout
+            Qh, Bh = sample_assemble_active(sc, torch.arange(F, dtype=torch.int32, device=sc.device), F, 0, int(n_hyp), int(n_hyp), guided[0], guided[1])
+        res = solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+        count = score_pnpl_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+        R, t, head, mp, ml = select_pnpl_scenes(sc, count, res.R, res.t, res.status, thresh)
     if refit:
         for _ in range(max(1, int(refit_rounds))):  # ... and the F refits of the consensus sets in one more solve there
             Bt, Qt, cnt = assemble_pnpl_consensus(sc, mp, ml)
@@ -1045,23 +1243,36 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
            "sizes": sc.sizes, "line_sizes": sc.line_sizes, "n_hyp": int(n_hyp)}
     if polish:
         out["refine"] = refined
+    if confidence is not None:
+        out.update(hyp_used=state.hyp_used.cpu(), rounds=rounds, confidence=conf)
+    if guided is not None:
+        out["pool_full"] = pool_full
     return out
 
 
 def ransac_pnl_batch(line_2d, line_3d, K, **kw):
-    """Robust PnL for F scenes of lines: ransac_pnpl_batch without points (packed lines: `line_sizes`)."""
+    """Robust PnL for F scenes of lines: ransac_pnpl_batch without points (packed lines: `line_sizes`; a guided call: `line_quality`)."""
     return ransac_pnpl_batch(None, line_2d, None, line_3d, K, **kw)
 
 
 def ransac_pnpl(pts_2d, line_2d, pts_3d, line_3d, K, **kw):
     """Robust PnPL for ONE scene: pts_2d [P,2], line_2d [L,2,2], pts_3d [P,3], line_3d [L,2,3] (either pair may be None), K [3,3].  The
     batch call with F = 1 (scene 0 uses `seed` itself), unpacked: R [3,3], t [3], inliers_pts [P], inliers_lines [L] on the device;
-    n_inliers, status, n_certified, best_index (ints), n_hyp."""
+    n_inliers, status, n_certified, best_index (ints), n_hyp.  The adaptive and guided keywords pass through (quality [P], line_quality
+    [L]); hyp_used is then an int."""
+    for k in ("quality", "line_quality"):
+        if kw.get(k) is not None:
+            kw[k] = [kw[k]]
     out = ransac_pnpl_batch(None if pts_2d is None else [pts_2d], None if line_2d is None else [line_2d], None if pts_3d is None else [pts_3d],
                             None if line_3d is None else [line_3d], K, **kw)
     h = out["head"][0]
-    return {"R": out["R"][0], "t": out["t"][0], "inliers_pts": out["inliers_pts"], "inliers_lines": out["inliers_lines"], "n_inliers": int(h[1]),
-            "status": int(h[0]), "n_certified": int(h[3]), "best_index": int(h[2]), "n_hyp": out["n_hyp"]}
+    one = {"R": out["R"][0], "t": out["t"][0], "inliers_pts": out["inliers_pts"], "inliers_lines": out["inliers_lines"], "n_inliers": int(h[1]),
+           "status": int(h[0]), "n_certified": int(h[3]), "best_index": int(h[2]), "n_hyp": out["n_hyp"]}
+    if "hyp_used" in out:
+        one.update(hyp_used=int(out["hyp_used"][0]), rounds=out["rounds"], confidence=out["confidence"])
+    if "pool_full" in out:
+        one["pool_full"] = out["pool_full"]
+    return one
 
 
 def ransac_pnl(line_2d, line_3d, K, **kw):
