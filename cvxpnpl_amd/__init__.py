@@ -11,6 +11,9 @@ from .api import (BatchResult, assemble_batch, assemble_subsets, ipm_batch, pack
 from .grad import pnl_batch_diff, pnp_batch_diff, pnpl_batch_diff, pose_vjp, pose_vjp_host  # noqa: F401
 from .refine import RefineResult, refine_pose_batch, refine_pose_batch_host, refine_scenes  # noqa: F401
 from .refine_robust import RobustRefineResult, refine_pose_batch_robust, refine_pose_batch_robust_host, refine_scenes_robust  # noqa: F401
+from .refine_robust_auto import (RobustAutoResult, RobustCovariance, RobustScale, refine_pose_batch_robust_auto, refine_pose_batch_robust_auto_host,  # noqa: F401
+                                 refine_scenes_robust_auto, robust_covariance_batch, robust_covariance_host, robust_covariance_scenes, robust_scale_batch,
+                                 robust_scale_batch_host, robust_scale_scenes)
 from .refine_robust_grad import refine_pose_batch_robust_diff, refine_vjp_robust, refine_vjp_robust_host, refine_vjp_scenes_robust  # noqa: F401
 from .refine_grad import pose_passthrough, refine_pose_batch_diff, refine_vjp, refine_vjp_host, refine_vjp_scenes  # noqa: F401
 from .ransac import ransac_pnl, ransac_pnl_batch, ransac_pnp_batch, ransac_pnpl, ransac_pnpl_batch  # noqa: F401

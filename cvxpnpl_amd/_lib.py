@@ -455,6 +455,48 @@ def ransac_pnpl_adaptive_lib():
     return L
 
 
+# the robust refinement at a scale per problem, its scale estimate and its sandwich covariance (include/cvxpnpl_amd_refine_robust_auto.h):
+# the twelfth library
+REFINE_ROBUST_AUTO_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_refine_robust_auto.so")
+REFINE_ROBUST_AUTO_EXPORTS = ("cvxpnpl_robust_scale_batch", "cvxpnpl_robust_scale_scenes", "cvxpnpl_robust_scale_batch_host",
+                              "cvxpnpl_refine_robust_pp_batch", "cvxpnpl_refine_robust_pp_scenes", "cvxpnpl_refine_robust_pp_batch_host",
+                              "cvxpnpl_robust_cov_batch", "cvxpnpl_robust_cov_scenes", "cvxpnpl_robust_cov_batch_host",
+                              "cvxpnpl_refine_robust_auto_last_error", "cvxpnpl_refine_robust_auto_version")
+RefineRobustAutoOpts = RefineRobustOpts  # the loop at a scale per problem takes cvxpnpl_refine_robust_opts_t as it is
+
+_refine_robust_auto_lib = None
+
+
+def refine_robust_auto_lib():
+    """Load libcvxpnpl_amd_refine_robust_auto.so (loudly)."""
+    global _refine_robust_auto_lib
+    if _refine_robust_auto_lib is not None:
+        return _refine_robust_auto_lib
+    if not os.path.exists(REFINE_ROBUST_AUTO_LIB_PATH):
+        raise LibraryMissing(f"{REFINE_ROBUST_AUTO_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+    L = C.CDLL(REFINE_ROBUST_AUTO_LIB_PATH)
+    p, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    batch, scenes = [i64, i32, p, p, i32, p, p], [i64, p, i64, p, i64, p, p, p, p]
+    pose = [p, i32, p, p, p, i64, C.c_uint32, p, p, p, p]  # K, K_per, R, t, status, stride, admit, masks, weights
+    loop = pose + [p, C.POINTER(RefineRobustAutoOpts)] + [p, p, p, p, p, p]  # scale_px [n], opts; R, t, cost, iters, status, n_live
+    cov = [p, i32, p, p, p, p, p, p, p, i32, f64, p, p, p]  # K, K_per, R, t, status, masks, weights, loss, scale_px, scale_px [n], cov, cov_status
+    L.cvxpnpl_robust_scale_batch.argtypes = batch + pose + [p, p, p, p, p, p]          # sigma, med_sq, n_live, status, sq, stream
+    L.cvxpnpl_robust_scale_batch_host.argtypes = batch + pose + [p, p, p, p, p, i32]   # ..., n_threads
+    L.cvxpnpl_robust_scale_scenes.argtypes = scenes + pose + [p, p, p, p, p, p, p]     # sigma, med_sq, n_live, status, sq_pts, sq_lines, stream
+    L.cvxpnpl_refine_robust_pp_batch.argtypes = batch + loop + [p, p, p]               # robust_w, n_inlier, stream
+    L.cvxpnpl_refine_robust_pp_batch_host.argtypes = batch + loop + [p, p, i32]        # robust_w, n_inlier, n_threads
+    L.cvxpnpl_refine_robust_pp_scenes.argtypes = scenes + loop + [p, p, p, p]          # robust_w_pts, robust_w_lines, n_inlier, stream
+    L.cvxpnpl_robust_cov_batch.argtypes = batch + cov + [p]
+    L.cvxpnpl_robust_cov_batch_host.argtypes = batch + cov + [i32]
+    L.cvxpnpl_robust_cov_scenes.argtypes = scenes + cov + [p]
+    for name in REFINE_ROBUST_AUTO_EXPORTS[:9]:
+        getattr(L, name).restype = C.c_int
+    L.cvxpnpl_refine_robust_auto_last_error.restype = C.c_char_p
+    L.cvxpnpl_refine_robust_auto_version.restype = C.c_char_p
+    _refine_robust_auto_lib = L
+    return L
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -185,6 +185,27 @@ def ransac_pnpl_adaptive_compile_cmd(out=RANSAC_PNPL_ADAPTIVE_OUT):
     return ransac_compile_cmd(out)[:-1] + [RANSAC_PNPL_ADAPTIVE_SRC]
 
 
+# the robust refinement at a scale per problem: a scale from the median squared residual, the loop at that scale and the sandwich covariance
+# (include/cvxpnpl_amd_refine_robust_auto.h): the twelfth library, the flags of the fifth to eighth
+REFINE_ROBUST_AUTO_SRC = os.path.join(HERE, "csrc", "refine_robust_auto_hip.hip")
+REFINE_ROBUST_AUTO_HOST_SRC = os.path.join(HERE, "csrc", "host_refine_robust_auto.cpp")
+REFINE_ROBUST_AUTO_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine_robust_auto.so")
+REFINE_ROBUST_AUTO_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_robust_auto.resources.txt")
+REFINE_ROBUST_AUTO_DEPS = [REFINE_ROBUST_AUTO_SRC, REFINE_ROBUST_AUTO_HOST_SRC, os.path.join(HERE, "csrc", "refine_robust_auto_core.h"),
+                           os.path.join(HERE, "csrc", "refine_robust_auto_kernel.h"), os.path.join(HERE, "csrc", "refine_robust_vjp_core.h"),
+                           os.path.join(HERE, "csrc", "refine_robust_core.h"), os.path.join(HERE, "csrc", "refine_robust_kernel.h"),
+                           os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_core.h"),
+                           os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                           os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                           os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                           os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust.h"),
+                           os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust_auto.h")]
+
+
+def refine_robust_auto_compile_cmd(out=REFINE_ROBUST_AUTO_OUT):
+    return grad_compile_cmd(out)[:-2] + [REFINE_ROBUST_AUTO_SRC, REFINE_ROBUST_AUTO_HOST_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -243,8 +264,12 @@ def build_ransac_pnpl_adaptive(force=False, verbose=False):
     return _build_one(RANSAC_PNPL_ADAPTIVE_OUT, RANSAC_PNPL_ADAPTIVE_RESOURCES, RANSAC_PNPL_ADAPTIVE_DEPS, ransac_pnpl_adaptive_compile_cmd(), force, verbose)
 
 
+def build_refine_robust_auto(force=False, verbose=False):
+    return _build_one(REFINE_ROBUST_AUTO_OUT, REFINE_ROBUST_AUTO_RESOURCES, REFINE_ROBUST_AUTO_DEPS, refine_robust_auto_compile_cmd(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All eleven libraries; returns the solver's (OUT)."""
+    """All twelve libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -256,6 +281,7 @@ def build(force=False, verbose=False):
     build_ransac_adaptive(force, verbose)
     build_ransac_guided(force, verbose)
     build_ransac_pnpl_adaptive(force, verbose)
+    build_refine_robust_auto(force, verbose)
     return OUT
 
 

@@ -11,8 +11,8 @@ schedule, re-weighted at every pose, the whole loop inside one launch.
   ALL records of its scene with no mask: ``refine_scenes_robust(sc, R, t, loss="huber", scale_px=thresh, status=head[:, 0])``.
 - ``refine_pose_batch_robust_host``: the same mathematics on host threads (numpy in and out), for checking.
 
-Not here: a covariance under a robust loss, gradients (``refine_robust_grad.py``, section 18), a
-``polish_loss=`` option inside ``ransac_*_batch``, an automatic scale (MAD).
+Not here: gradients (``refine_robust_grad.py``, section 18), a covariance under a robust loss and an automatic
+scale per problem (``refine_robust_auto.py``, section 22), a ``polish_loss=`` option inside ``ransac_*_batch``.
 """
 import ctypes as C
 import math
