@@ -44,6 +44,24 @@ class LibraryMissing(RuntimeError):
     pass
 
 
+_loaded = {}
+
+
+def _load(path, exports, set_argtypes):
+    """Load a library of `exports` once (loudly).  Every export returns int but *_last_error and *_version, which return a string;
+    set_argtypes(L) gives the argument types, and the return type of an export that returns something else."""
+    L = _loaded.get(path)
+    if L is None:
+        if not os.path.exists(path):
+            raise LibraryMissing(f"{path} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+        L = C.CDLL(path)
+        for name in exports:
+            getattr(L, name).restype = C.c_char_p if name.endswith(("_last_error", "_version")) else C.c_int
+        set_argtypes(L)
+        _loaded[path] = L
+    return L
+
+
 _lib = None
 
 
@@ -146,26 +164,17 @@ GRAD_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_grad.so")
 GRAD_EXPORTS = ("cvxpnpl_pose_vjp_batch", "cvxpnpl_pose_vjp_host", "cvxpnpl_grad_last_error")
 VJP_OK, VJP_SKIPPED, VJP_SINGULAR, VJP_NONFINITE = 0, 1, 2, 3  # CVXPNPL_VJP_*
 
-_grad_lib = None
+
+def _grad_argtypes(L):
+    L.cvxpnpl_pose_vjp_batch.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.cvxpnpl_pose_vjp_host.argtypes = L.cvxpnpl_pose_vjp_batch.argtypes[:-1] + [C.c_int32]
 
 
 def grad_lib():
     """Load libcvxpnpl_amd_grad.so (loudly)."""
-    global _grad_lib
-    if _grad_lib is not None:
-        return _grad_lib
-    if not os.path.exists(GRAD_LIB_PATH):
-        raise LibraryMissing(f"{GRAD_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(GRAD_LIB_PATH)
-    L.cvxpnpl_pose_vjp_batch.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_pose_vjp_batch.restype = C.c_int
-    L.cvxpnpl_pose_vjp_host.argtypes = L.cvxpnpl_pose_vjp_batch.argtypes[:-1] + [C.c_int32]
-    L.cvxpnpl_pose_vjp_host.restype = C.c_int
-    L.cvxpnpl_grad_last_error.restype = C.c_char_p
-    _grad_lib = L
-    return L
+    return _load(GRAD_LIB_PATH, GRAD_EXPORTS, _grad_argtypes)
 
 
 # RANSAC over many scenes (include/cvxpnpl_amd_ransac.h): the third library
@@ -173,28 +182,19 @@ RANSAC_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac.so")
 RANSAC_EXPORTS = ("cvxpnpl_ransac_sample_scenes", "cvxpnpl_ransac_score_scenes", "cvxpnpl_ransac_select_scenes", "cvxpnpl_ransac_assemble_consensus",
                   "cvxpnpl_ransac_refit_update_scenes", "cvxpnpl_ransac_last_error")
 
-_ransac_lib = None
 
-
-def ransac_lib():
-    """Load libcvxpnpl_amd_ransac.so (loudly)."""
-    global _ransac_lib
-    if _ransac_lib is not None:
-        return _ransac_lib
-    if not os.path.exists(RANSAC_LIB_PATH):
-        raise LibraryMissing(f"{RANSAC_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(RANSAC_LIB_PATH)
+def _ransac_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.cvxpnpl_ransac_sample_scenes.argtypes = [i64, i32, p, i64, p, p, p, p, p, p, p, p, p]
     L.cvxpnpl_ransac_score_scenes.argtypes = [i64, i32, p, i64, p, p, p, C.c_uint32, p, i32, p, p, C.c_double, p, p]
     L.cvxpnpl_ransac_select_scenes.argtypes = [i64, i32, p, i64, p, p, p, p, p, i32, p, p, C.c_double, p, p, p, p, p]
     L.cvxpnpl_ransac_assemble_consensus.argtypes = [i64, p, i64, p, p, p, p, i32, p, p, p, p]
     L.cvxpnpl_ransac_refit_update_scenes.argtypes = [i64, p, i64, p, p, p, p, p, i32, p, p, C.c_double, p, p, p, p, p]
-    for name in RANSAC_EXPORTS[:-1]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_ransac_last_error.restype = C.c_char_p
-    _ransac_lib = L
-    return L
+
+
+def ransac_lib():
+    """Load libcvxpnpl_amd_ransac.so (loudly)."""
+    return _load(RANSAC_LIB_PATH, RANSAC_EXPORTS, _ransac_argtypes)
 
 
 # RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl.h): the fourth library
@@ -202,17 +202,8 @@ RANSAC_PNPL_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_pnpl.so")
 RANSAC_PNPL_EXPORTS = ("cvxpnpl_ransac_pnpl_sample_assemble", "cvxpnpl_ransac_pnpl_score", "cvxpnpl_ransac_pnpl_select",
                        "cvxpnpl_ransac_pnpl_assemble_consensus", "cvxpnpl_ransac_pnpl_refit_update", "cvxpnpl_ransac_pnpl_last_error")
 
-_ransac_pnpl_lib = None
 
-
-def ransac_pnpl_lib():
-    """Load libcvxpnpl_amd_ransac_pnpl.so (loudly)."""
-    global _ransac_pnpl_lib
-    if _ransac_pnpl_lib is not None:
-        return _ransac_pnpl_lib
-    if not os.path.exists(RANSAC_PNPL_LIB_PATH):
-        raise LibraryMissing(f"{RANSAC_PNPL_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(RANSAC_PNPL_LIB_PATH)
+def _ransac_pnpl_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     scenes = [p, i64, p, i64]  # d_pt_offsets, n_pts, d_ln_offsets, n_lines
     L.cvxpnpl_ransac_pnpl_sample_assemble.argtypes = [i64, i32] + scenes + [p, p, p, p, p, p, i32, p, p, p, p]
@@ -220,11 +211,11 @@ def ransac_pnpl_lib():
     L.cvxpnpl_ransac_pnpl_select.argtypes = [i64, i32] + scenes + [p, p, p, p, p, i32, p, p, p, p, C.c_double, p, p, p, p, p, p]
     L.cvxpnpl_ransac_pnpl_assemble_consensus.argtypes = [i64] + scenes + [p, p, p, p, p, p, p, i32, p, p, p, p]
     L.cvxpnpl_ransac_pnpl_refit_update.argtypes = [i64] + scenes + [p, p, p, p, p, i32, p, p, p, p, C.c_double, p, p, p, p, p, p]
-    for name in RANSAC_PNPL_EXPORTS[:-1]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_ransac_pnpl_last_error.restype = C.c_char_p
-    _ransac_pnpl_lib = L
-    return L
+
+
+def ransac_pnpl_lib():
+    """Load libcvxpnpl_amd_ransac_pnpl.so (loudly)."""
+    return _load(RANSAC_PNPL_LIB_PATH, RANSAC_PNPL_EXPORTS, _ransac_pnpl_argtypes)
 
 
 # reprojection refinement of poses (include/cvxpnpl_amd_refine.h): the fifth library
@@ -238,29 +229,19 @@ class RefineOpts(C.Structure):
     _fields_ = [("struct_size", C.c_uint32), ("max_iters", C.c_int32), ("step_tol", C.c_double), ("lambda0", C.c_double), ("sigma_px", C.c_double)]
 
 
-_refine_lib = None
 
-
-def refine_lib():
-    """Load libcvxpnpl_amd_refine.so (loudly)."""
-    global _refine_lib
-    if _refine_lib is not None:
-        return _refine_lib
-    if not os.path.exists(REFINE_LIB_PATH):
-        raise LibraryMissing(f"{REFINE_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(REFINE_LIB_PATH)
+def _refine_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     pose = [p, i32, p, p, p, i64, C.c_uint32, p, p, C.POINTER(RefineOpts)]  # K, K_per, R, t, status, stride, admit, masks, opts
     outs = [p, p, p, p, p, p, p]                                            # R, t, cost, iters, status, n_live, cov
     L.cvxpnpl_refine_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [p]
     L.cvxpnpl_refine_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [i32]
     L.cvxpnpl_refine_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + outs + [p]
-    for name in REFINE_EXPORTS[:3]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_refine_last_error.restype = C.c_char_p
-    L.cvxpnpl_refine_version.restype = C.c_char_p
-    _refine_lib = L
-    return L
+
+
+def refine_lib():
+    """Load libcvxpnpl_amd_refine.so (loudly)."""
+    return _load(REFINE_LIB_PATH, REFINE_EXPORTS, _refine_argtypes)
 
 
 # the backward pass of the refinement (include/cvxpnpl_amd_refine_grad.h): the sixth library
@@ -269,29 +250,19 @@ REFINE_GRAD_EXPORTS = ("cvxpnpl_refine_vjp_batch", "cvxpnpl_refine_vjp_scenes", 
                        "cvxpnpl_refine_grad_version")
 REFINE_VJP_OK, REFINE_VJP_SKIPPED, REFINE_VJP_SINGULAR, REFINE_VJP_BEHIND = 0, 1, 2, 3  # CVXPNPL_REFINE_VJP_*
 
-_refine_grad_lib = None
 
-
-def refine_grad_lib():
-    """Load libcvxpnpl_amd_refine_grad.so (loudly)."""
-    global _refine_grad_lib
-    if _refine_grad_lib is not None:
-        return _refine_grad_lib
-    if not os.path.exists(REFINE_GRAD_LIB_PATH):
-        raise LibraryMissing(f"{REFINE_GRAD_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(REFINE_GRAD_LIB_PATH)
+def _refine_grad_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     pose = [p, i32, p, p, p, i64, C.c_uint32, p, p]  # K, K_per, R, t, refine status, stride, admit, masks
     grads = [p, p, p, p, p, p, p, p]                 # grad_R, grad_t, g_pts_2d, g_pts_3d, g_line_2d, g_line_3d, vjp_status, info
     L.cvxpnpl_refine_vjp_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + grads + [p]
     L.cvxpnpl_refine_vjp_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + grads + [i32]
     L.cvxpnpl_refine_vjp_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + grads + [p]
-    for name in REFINE_GRAD_EXPORTS[:3]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_refine_grad_last_error.restype = C.c_char_p
-    L.cvxpnpl_refine_grad_version.restype = C.c_char_p
-    _refine_grad_lib = L
-    return L
+
+
+def refine_grad_lib():
+    """Load libcvxpnpl_amd_refine_grad.so (loudly)."""
+    return _load(REFINE_GRAD_LIB_PATH, REFINE_GRAD_EXPORTS, _refine_grad_argtypes)
 
 
 # the refinement under a robust loss and weights (include/cvxpnpl_amd_refine_robust.h): the seventh library
@@ -308,29 +279,19 @@ class RefineRobustOpts(C.Structure):
                 ("scale_px", C.c_double)]
 
 
-_refine_robust_lib = None
 
-
-def refine_robust_lib():
-    """Load libcvxpnpl_amd_refine_robust.so (loudly)."""
-    global _refine_robust_lib
-    if _refine_robust_lib is not None:
-        return _refine_robust_lib
-    if not os.path.exists(REFINE_ROBUST_LIB_PATH):
-        raise LibraryMissing(f"{REFINE_ROBUST_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(REFINE_ROBUST_LIB_PATH)
+def _refine_robust_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     pose = [p, i32, p, p, p, i64, C.c_uint32, p, p, p, p, C.POINTER(RefineRobustOpts)]  # K, K_per, R, t, status, stride, admit, masks, weights, opts
     outs = [p, p, p, p, p, p]                                                          # R, t, cost, iters, status, n_live
     L.cvxpnpl_refine_robust_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [p, p, p]         # robust_w, n_inlier, stream
     L.cvxpnpl_refine_robust_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + outs + [p, p, i32]  # robust_w, n_inlier, n_threads
     L.cvxpnpl_refine_robust_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + outs + [p, p, p, p]  # robust_w_pts, robust_w_lines, n_inlier, stream
-    for name in REFINE_ROBUST_EXPORTS[:3]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_refine_robust_last_error.restype = C.c_char_p
-    L.cvxpnpl_refine_robust_version.restype = C.c_char_p
-    _refine_robust_lib = L
-    return L
+
+
+def refine_robust_lib():
+    """Load libcvxpnpl_amd_refine_robust.so (loudly)."""
+    return _load(REFINE_ROBUST_LIB_PATH, REFINE_ROBUST_EXPORTS, _refine_robust_argtypes)
 
 
 # the backward pass of the robust refinement (include/cvxpnpl_amd_refine_robust_grad.h): the eighth library
@@ -338,29 +299,19 @@ REFINE_ROBUST_GRAD_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_refine_robust_
 REFINE_ROBUST_GRAD_EXPORTS = ("cvxpnpl_refine_robust_vjp_batch", "cvxpnpl_refine_robust_vjp_scenes", "cvxpnpl_refine_robust_vjp_batch_host",
                               "cvxpnpl_refine_robust_grad_last_error", "cvxpnpl_refine_robust_grad_version")
 
-_refine_robust_grad_lib = None
 
-
-def refine_robust_grad_lib():
-    """Load libcvxpnpl_amd_refine_robust_grad.so (loudly)."""
-    global _refine_robust_grad_lib
-    if _refine_robust_grad_lib is not None:
-        return _refine_robust_grad_lib
-    if not os.path.exists(REFINE_ROBUST_GRAD_LIB_PATH):
-        raise LibraryMissing(f"{REFINE_ROBUST_GRAD_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(REFINE_ROBUST_GRAD_LIB_PATH)
+def _refine_robust_grad_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     pose = [p, i32, p, p, p, i64, C.c_uint32, i32, C.c_double, p, p, p, p]  # K, K_per, R, t, refine status, stride, admit, loss, scale_px, masks, weights
     grads = [p, p, p, p, p, p, p, p, p, p]  # grad_R, grad_t, g_pts_2d, g_pts_3d, g_line_2d, g_line_3d, g_w_pts, g_w_lines, vjp_status, info
     L.cvxpnpl_refine_robust_vjp_batch.argtypes = [i64, i32, p, p, i32, p, p] + pose + grads + [p]
     L.cvxpnpl_refine_robust_vjp_batch_host.argtypes = [i64, i32, p, p, i32, p, p] + pose + grads + [i32]
     L.cvxpnpl_refine_robust_vjp_scenes.argtypes = [i64, p, i64, p, i64, p, p, p, p] + pose + grads + [p]
-    for name in REFINE_ROBUST_GRAD_EXPORTS[:3]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_refine_robust_grad_last_error.restype = C.c_char_p
-    L.cvxpnpl_refine_robust_grad_version.restype = C.c_char_p
-    _refine_robust_grad_lib = L
-    return L
+
+
+def refine_robust_grad_lib():
+    """Load libcvxpnpl_amd_refine_robust_grad.so (loudly)."""
+    return _load(REFINE_ROBUST_GRAD_LIB_PATH, REFINE_ROBUST_GRAD_EXPORTS, _refine_robust_grad_argtypes)
 
 
 # adaptive RANSAC, a hypothesis budget per scene solved in rounds (include/cvxpnpl_amd_ransac_adaptive.h): the ninth library
@@ -369,17 +320,8 @@ RANSAC_ADAPTIVE_EXPORTS = ("cvxpnpl_ransac_adaptive_init", "cvxpnpl_ransac_adapt
                            "cvxpnpl_ransac_adaptive_update", "cvxpnpl_ransac_adaptive_compact", "cvxpnpl_ransac_adaptive_needed_host",
                            "cvxpnpl_ransac_adaptive_last_error")
 
-_ransac_adaptive_lib = None
 
-
-def ransac_adaptive_lib():
-    """Load libcvxpnpl_amd_ransac_adaptive.so (loudly)."""
-    global _ransac_adaptive_lib
-    if _ransac_adaptive_lib is not None:
-        return _ransac_adaptive_lib
-    if not os.path.exists(RANSAC_ADAPTIVE_LIB_PATH):
-        raise LibraryMissing(f"{RANSAC_ADAPTIVE_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(RANSAC_ADAPTIVE_LIB_PATH)
+def _ransac_adaptive_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.cvxpnpl_ransac_adaptive_init.argtypes = [i64, p, p, p, p, p, p]
     L.cvxpnpl_ransac_adaptive_sample.argtypes = [i64, i64, p, i32, i32, i32, p, i64, p, p, p, p, p, p, p, p, p]
@@ -387,13 +329,13 @@ def ransac_adaptive_lib():
     L.cvxpnpl_ransac_adaptive_update.argtypes = [i64, i64, p, i32, i32, i32, C.c_double, p, i64, p, p, p, p, p, i32, p, p, C.c_double,
                                                  p, p, p, p, p, p, p, p]
     L.cvxpnpl_ransac_adaptive_compact.argtypes = [i64, i64, p, p, p, p, p]
-    for name in RANSAC_ADAPTIVE_EXPORTS[:5]:
-        getattr(L, name).restype = C.c_int
     L.cvxpnpl_ransac_adaptive_needed_host.argtypes = [i32, i32, C.c_double]
     L.cvxpnpl_ransac_adaptive_needed_host.restype = C.c_double
-    L.cvxpnpl_ransac_adaptive_last_error.restype = C.c_char_p
-    _ransac_adaptive_lib = L
-    return L
+
+
+def ransac_adaptive_lib():
+    """Load libcvxpnpl_amd_ransac_adaptive.so (loudly)."""
+    return _load(RANSAC_ADAPTIVE_LIB_PATH, RANSAC_ADAPTIVE_EXPORTS, _ransac_adaptive_argtypes)
 
 
 # guided RANSAC, minimal sets drawn from the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h): the tenth library
@@ -401,29 +343,20 @@ RANSAC_GUIDED_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_guided.so")
 RANSAC_GUIDED_EXPORTS = ("cvxpnpl_ransac_guided_rank", "cvxpnpl_ransac_guided_sample", "cvxpnpl_ransac_guided_sample_active",
                          "cvxpnpl_ransac_guided_rank_host", "cvxpnpl_ransac_guided_pool_host", "cvxpnpl_ransac_guided_last_error")
 
-_ransac_guided_lib = None
 
-
-def ransac_guided_lib():
-    """Load libcvxpnpl_amd_ransac_guided.so (loudly)."""
-    global _ransac_guided_lib
-    if _ransac_guided_lib is not None:
-        return _ransac_guided_lib
-    if not os.path.exists(RANSAC_GUIDED_LIB_PATH):
-        raise LibraryMissing(f"{RANSAC_GUIDED_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(RANSAC_GUIDED_LIB_PATH)
+def _ransac_guided_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     L.cvxpnpl_ransac_guided_rank.argtypes = [i64, p, i64, i32, p, p, p]
     L.cvxpnpl_ransac_guided_sample.argtypes = [i64, i32, i32, p, i64, p, p, p, p, p, p, p, p, p, p]
     L.cvxpnpl_ransac_guided_sample_active.argtypes = [i64, i64, p, i32, i32, i32, i32, p, i64, p, p, p, p, p, p, p, p, p, p]
     L.cvxpnpl_ransac_guided_rank_host.argtypes = [i64, p, i64, p, p, i32]
-    for name in RANSAC_GUIDED_EXPORTS[:4]:
-        getattr(L, name).restype = C.c_int
     L.cvxpnpl_ransac_guided_pool_host.argtypes = [i32, i32, i32]
     L.cvxpnpl_ransac_guided_pool_host.restype = i32
-    L.cvxpnpl_ransac_guided_last_error.restype = C.c_char_p
-    _ransac_guided_lib = L
-    return L
+
+
+def ransac_guided_lib():
+    """Load libcvxpnpl_amd_ransac_guided.so (loudly)."""
+    return _load(RANSAC_GUIDED_LIB_PATH, RANSAC_GUIDED_EXPORTS, _ransac_guided_argtypes)
 
 
 # adaptive and guided RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl_adaptive.h): the eleventh library
@@ -431,28 +364,19 @@ RANSAC_PNPL_ADAPTIVE_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_pnpl_
 RANSAC_PNPL_ADAPTIVE_EXPORTS = ("cvxpnpl_ransac_pnpl_adaptive_sample_assemble", "cvxpnpl_ransac_pnpl_adaptive_score",
                                 "cvxpnpl_ransac_pnpl_adaptive_update", "cvxpnpl_ransac_pnpl_adaptive_last_error")
 
-_ransac_pnpl_adaptive_lib = None
 
-
-def ransac_pnpl_adaptive_lib():
-    """Load libcvxpnpl_amd_ransac_pnpl_adaptive.so (loudly)."""
-    global _ransac_pnpl_adaptive_lib
-    if _ransac_pnpl_adaptive_lib is not None:
-        return _ransac_pnpl_adaptive_lib
-    if not os.path.exists(RANSAC_PNPL_ADAPTIVE_LIB_PATH):
-        raise LibraryMissing(f"{RANSAC_PNPL_ADAPTIVE_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(RANSAC_PNPL_ADAPTIVE_LIB_PATH)
+def _ransac_pnpl_adaptive_argtypes(L):
     p, i32, i64 = C.c_void_p, C.c_int32, C.c_int64
     scenes = [p, i64, p, i64]  # d_pt_offsets, n_pts, d_ln_offsets, n_lines
     L.cvxpnpl_ransac_pnpl_adaptive_sample_assemble.argtypes = [i64, i64, p, i32, i32, i32, i32] + scenes + [p, p, p, p, p, p, p, i32, p, p, p, p]
     L.cvxpnpl_ransac_pnpl_adaptive_score.argtypes = [i64, i64, p, i32] + scenes + [p, p, p, C.c_uint32, p, i32, p, p, p, p, C.c_double, p, p]
     L.cvxpnpl_ransac_pnpl_adaptive_update.argtypes = [i64, i64, p, i32, i32, i32, C.c_double] + scenes + [p, p, p, p, p, i32, p, p, p, p, C.c_double,
                                                                                                             p, p, p, p, p, p, p, p, p]
-    for name in RANSAC_PNPL_ADAPTIVE_EXPORTS[:-1]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_ransac_pnpl_adaptive_last_error.restype = C.c_char_p
-    _ransac_pnpl_adaptive_lib = L
-    return L
+
+
+def ransac_pnpl_adaptive_lib():
+    """Load libcvxpnpl_amd_ransac_pnpl_adaptive.so (loudly)."""
+    return _load(RANSAC_PNPL_ADAPTIVE_LIB_PATH, RANSAC_PNPL_ADAPTIVE_EXPORTS, _ransac_pnpl_adaptive_argtypes)
 
 
 # the robust refinement at a scale per problem, its scale estimate and its sandwich covariance (include/cvxpnpl_amd_refine_robust_auto.h):
@@ -464,17 +388,8 @@ REFINE_ROBUST_AUTO_EXPORTS = ("cvxpnpl_robust_scale_batch", "cvxpnpl_robust_scal
                               "cvxpnpl_refine_robust_auto_last_error", "cvxpnpl_refine_robust_auto_version")
 RefineRobustAutoOpts = RefineRobustOpts  # the loop at a scale per problem takes cvxpnpl_refine_robust_opts_t as it is
 
-_refine_robust_auto_lib = None
 
-
-def refine_robust_auto_lib():
-    """Load libcvxpnpl_amd_refine_robust_auto.so (loudly)."""
-    global _refine_robust_auto_lib
-    if _refine_robust_auto_lib is not None:
-        return _refine_robust_auto_lib
-    if not os.path.exists(REFINE_ROBUST_AUTO_LIB_PATH):
-        raise LibraryMissing(f"{REFINE_ROBUST_AUTO_LIB_PATH} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
-    L = C.CDLL(REFINE_ROBUST_AUTO_LIB_PATH)
+def _refine_robust_auto_argtypes(L):
     p, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
     batch, scenes = [i64, i32, p, p, i32, p, p], [i64, p, i64, p, i64, p, p, p, p]
     pose = [p, i32, p, p, p, i64, C.c_uint32, p, p, p, p]  # K, K_per, R, t, status, stride, admit, masks, weights
@@ -489,12 +404,11 @@ def refine_robust_auto_lib():
     L.cvxpnpl_robust_cov_batch.argtypes = batch + cov + [p]
     L.cvxpnpl_robust_cov_batch_host.argtypes = batch + cov + [i32]
     L.cvxpnpl_robust_cov_scenes.argtypes = scenes + cov + [p]
-    for name in REFINE_ROBUST_AUTO_EXPORTS[:9]:
-        getattr(L, name).restype = C.c_int
-    L.cvxpnpl_refine_robust_auto_last_error.restype = C.c_char_p
-    L.cvxpnpl_refine_robust_auto_version.restype = C.c_char_p
-    _refine_robust_auto_lib = L
-    return L
+
+
+def refine_robust_auto_lib():
+    """Load libcvxpnpl_amd_refine_robust_auto.so (loudly)."""
+    return _load(REFINE_ROBUST_AUTO_LIB_PATH, REFINE_ROBUST_AUTO_EXPORTS, _refine_robust_auto_argtypes)
 
 
 def default_opts(**overrides):

@@ -15,6 +15,10 @@ DEPS = [SRC, HOST_SRC, LANE_SRC, os.path.join(HERE, "csrc", "batch_args.h"), os.
         os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd.h")]
 
 
+ENTRY_ERROR_H = os.path.join(HERE, "csrc", "entry_error.h")  # the error text of the refinement and the RANSAC entry points
+RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the five RANSAC entry files share
+
+
 def hipcc():
     for c in (shutil.which("hipcc"), "/opt/rocm/bin/hipcc"):
         if c and os.path.exists(c):
@@ -54,7 +58,7 @@ def grad_compile_cmd(out=GRAD_OUT):
 RANSAC_SRC = os.path.join(HERE, "csrc", "ransac_hip.hip")
 RANSAC_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac.so")
 RANSAC_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac.resources.txt")
-RANSAC_DEPS = [RANSAC_SRC, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+RANSAC_DEPS = [RANSAC_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac.h")]
 
 
@@ -67,7 +71,7 @@ def ransac_compile_cmd(out=RANSAC_OUT):
 RANSAC_PNPL_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_hip.hip")
 RANSAC_PNPL_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.so")
 RANSAC_PNPL_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.resources.txt")
-RANSAC_PNPL_DEPS = [RANSAC_PNPL_SRC, os.path.join(HERE, "csrc", "ransac_pnpl_kernel.h"), os.path.join(HERE, "csrc", "ransac_pnpl_common.h"),
+RANSAC_PNPL_DEPS = [RANSAC_PNPL_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_pnpl_kernel.h"), os.path.join(HERE, "csrc", "ransac_pnpl_common.h"),
                     os.path.join(HERE, "csrc", "ransac_common.h"),
                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                     os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_pnpl.h")]
@@ -84,7 +88,7 @@ REFINE_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine.so")
 REFINE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine.resources.txt")
 REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"), os.path.join(HERE, "csrc", "refine_lanes.h"),
                os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
-               os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+               os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine.h")]
 
 
@@ -100,7 +104,7 @@ REFINE_GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_grad.resources
 REFINE_GRAD_DEPS = [REFINE_GRAD_SRC, REFINE_GRAD_HOST_SRC, os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_vjp_kernel.h"),
                     os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
-                    os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                    os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                     os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_grad.h")]
 
 
@@ -116,7 +120,7 @@ REFINE_ROBUST_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_robust.resou
 REFINE_ROBUST_DEPS = [REFINE_ROBUST_SRC, REFINE_ROBUST_HOST_SRC, os.path.join(HERE, "csrc", "refine_robust_core.h"), os.path.join(HERE, "csrc", "refine_robust_kernel.h"),
                       os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                       os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
-                      os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                      os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                       os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust.h")]
 
 
@@ -134,7 +138,7 @@ REFINE_ROBUST_GRAD_DEPS = [REFINE_ROBUST_GRAD_SRC, REFINE_ROBUST_GRAD_HOST_SRC, 
                            os.path.join(HERE, "csrc", "refine_robust_kernel.h"), os.path.join(HERE, "csrc", "refine_vjp_core.h"),
                            os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                            os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
-                           os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                           os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                            os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust_grad.h")]
 
 
@@ -147,7 +151,7 @@ def refine_robust_grad_compile_cmd(out=REFINE_ROBUST_GRAD_OUT):
 RANSAC_ADAPTIVE_SRC = os.path.join(HERE, "csrc", "ransac_adaptive_hip.hip")
 RANSAC_ADAPTIVE_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_adaptive.so")
 RANSAC_ADAPTIVE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_adaptive.resources.txt")
-RANSAC_ADAPTIVE_DEPS = [RANSAC_ADAPTIVE_SRC, os.path.join(HERE, "csrc", "ransac_adaptive_kernel.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
+RANSAC_ADAPTIVE_DEPS = [RANSAC_ADAPTIVE_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_adaptive_kernel.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
                         os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_adaptive.h")]
 
 
@@ -160,7 +164,7 @@ def ransac_adaptive_compile_cmd(out=RANSAC_ADAPTIVE_OUT):
 RANSAC_GUIDED_SRC = os.path.join(HERE, "csrc", "ransac_guided_hip.hip")
 RANSAC_GUIDED_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_guided.so")
 RANSAC_GUIDED_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_guided.resources.txt")
-RANSAC_GUIDED_DEPS = [RANSAC_GUIDED_SRC, os.path.join(HERE, "csrc", "ransac_guided_kernel.h"), os.path.join(HERE, "csrc", "ransac_guided_core.h"),
+RANSAC_GUIDED_DEPS = [RANSAC_GUIDED_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_guided_kernel.h"), os.path.join(HERE, "csrc", "ransac_guided_core.h"),
                       os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "host_pool.h"),
                       os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_guided.h")]
 
@@ -174,7 +178,7 @@ def ransac_guided_compile_cmd(out=RANSAC_GUIDED_OUT):
 RANSAC_PNPL_ADAPTIVE_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_adaptive_hip.hip")
 RANSAC_PNPL_ADAPTIVE_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_adaptive.so")
 RANSAC_PNPL_ADAPTIVE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_adaptive.resources.txt")
-RANSAC_PNPL_ADAPTIVE_DEPS = [RANSAC_PNPL_ADAPTIVE_SRC, os.path.join(HERE, "csrc", "ransac_pnpl_adaptive_kernel.h"),
+RANSAC_PNPL_ADAPTIVE_DEPS = [RANSAC_PNPL_ADAPTIVE_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_pnpl_adaptive_kernel.h"),
                              os.path.join(HERE, "csrc", "ransac_pnpl_common.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
                              os.path.join(HERE, "csrc", "ransac_guided_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                              os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
@@ -197,7 +201,7 @@ REFINE_ROBUST_AUTO_DEPS = [REFINE_ROBUST_AUTO_SRC, REFINE_ROBUST_AUTO_HOST_SRC, 
                            os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_core.h"),
                            os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                            os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
-                           os.path.join(HERE, "csrc", "refine_entry.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                           os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                            os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust.h"),
                            os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust_auto.h")]
 

@@ -8,10 +8,10 @@
 // before any pointer is looked at, the pointers, K and the poses, its own outputs, the status column, its own options.
 #pragma once
 #include <stdint.h>
-#include <stdio.h>
 
 #include <cmath>
 
+#include "entry_error.h"
 #include "host_pool.h"
 #include "refine_core.h"
 
@@ -19,26 +19,11 @@
 
 namespace cvxre {
 
-CVXRE_FN char *err_buf()
-{
-    static thread_local char buf[512] = "";
-    return buf;
-}
-
-CVXRE_FN int bad_args(const char *who, const char *what)
-{
-    snprintf(err_buf(), 512, "%s: bad arguments (%s)", who, what);
-    return -1;
-}
-
+// the error text: entry_error.h
+using cvxee::bad_args;
+using cvxee::err_buf;
 #if defined(__HIPCC__)
-CVXRE_FN int launched(const char *what)
-{
-    const hipError_t e = hipGetLastError();
-    if (e == hipSuccess) return 0;
-    snprintf(err_buf(), 512, "%s: %s", what, hipGetErrorString(e));
-    return -2;
-}
+using cvxee::launched;
 #endif
 
 // ---- the argument contract ----

@@ -6,13 +6,14 @@ reprojection inliers over the whole scene, refit the best consensus set (assembl
 solved at the cost seam: no host round trip inside a frame).  Sampling, the solves and the scoring are the HIP path (cvxpnpl_sample_minimal_sets, cvxpnpl_solve_batch,
 cvxpnpl_score_hypotheses, cvxpnpl_select_best, cvxpnpl_assemble_subsets, cvxpnpl_solve_cost_batch, cvxpnpl_refit_update): no torch kernel in a frame.
 """
-import ctypes as _C
 from typing import Optional
 
 import numpy as _np
 import torch
 
 from . import _lib
+from ._ransac_args import (_call, _chk, _chk_active, _chk_budget, _chk_pnpl_scenes, _chk_pool_full, _chk_round, _chk_scenes, _chk_state,  # noqa: F401
+                           _chk_refit, _cost_outputs, _data_args, _poses, _resolve_seeds, _sample_outputs, _scene_args, _seed_words, _seeds_dev, _usable_mask)
 from .api import _ptr, _require_gpu
 from .api import assemble_subsets, pnp_batch, refit_update, sample_minimal_sets, score_hypotheses, select_best, solve_cost_batch
 
@@ -32,14 +33,7 @@ def ransac_pnp(pts_2d, pts_3d, K, n_hyp: int = 4096, thresh: float = 2.0, max_it
     inliers [M] bool, n_inliers, status of the final solve, n_certified hypotheses.  refit_rounds: refits of the consensus set (each one
     assembly + solve + scoring launch; no host synchronisation inside a frame, whatever the count).
     """
-    if device is None:  # like pnpl_batch: the device of a CUDA input, else the current device
-        for a in (pts_3d, pts_2d, K):
-            if isinstance(a, torch.Tensor) and a.is_cuda:
-                device = a.device
-                break
-        else:
-            device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = _pick_device(device, pts_3d, pts_2d, K)  # like pnpl_batch: the device of a CUDA input, else the current device
     x = torch.as_tensor(pts_2d, dtype=torch.float64, device=device)
     X = torch.as_tensor(pts_3d, dtype=torch.float64, device=device)
     Kd = torch.as_tensor(K, dtype=torch.float64, device=device)
@@ -156,51 +150,11 @@ def pack_scenes(pts_2d, pts_3d, K, sizes=None, device=None, seeds=None) -> Scene
     meta = _np.zeros(F + 1 + (F if seeds is not None else 0), dtype=_np.int64)  # offsets, then the seeds: one host-to-device copy
     _np.cumsum(sizes, out=meta[1:F + 1])
     if seeds is not None:
-        meta[F + 1:] = _np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=_np.uint64).view(_np.int64)
+        meta[F + 1:] = _seed_words(seeds)
     meta = torch.as_tensor(meta).to(device)
     off, sd = meta[:F + 1], (meta[F + 1:] if seeds is not None else None)
     Kd = K if isinstance(K, torch.Tensor) else torch.as_tensor(_np.ascontiguousarray(K, dtype=_np.float64))
     return Scenes(_to_dev(pts_2d, device), _to_dev(pts_3d, device), off, sizes, _to_dev(Kd, device), sd)
-
-
-def _chk(t, name, dtype, shape, device):
-    """What the C entry points assume of a tensor: a contiguous tensor of this dtype and shape on this device."""
-    if not isinstance(t, torch.Tensor):
-        raise TypeError(f"{name}: expected a torch tensor, got {type(t).__name__}")
-    if t.device != device:
-        raise ValueError(f"{name}: on {t.device}, the scenes are on {device}")
-    if t.dtype != dtype:
-        raise ValueError(f"{name}: dtype {t.dtype}, expected {dtype}")
-    if tuple(t.shape) != tuple(shape):
-        raise ValueError(f"{name}: shape {tuple(t.shape)}, expected {tuple(shape)}")
-    if not t.is_contiguous():
-        raise ValueError(f"{name}: not contiguous")
-    return t
-
-
-def _chk_scenes(sc: Scenes):
-    dev = sc.device
-    if dev.type != "cuda":
-        raise ValueError(f"the scenes are on {dev}: cvxpnpl_amd has no CPU path")
-    _chk(sc.x, "scene pts_2d", torch.float64, (sc.total, 2), dev)
-    _chk(sc.X, "scene pts_3d", torch.float64, (sc.total, 3), dev)
-    _chk(sc.offsets, "offsets", torch.int64, (sc.F + 1,), dev)
-    _chk(sc.K, "K", torch.float64, (sc.F, 3, 3) if sc.per_scene_K else (3, 3), dev)
-
-
-def _call(sc: Scenes, name, *args):
-    with torch.cuda.device(sc.device):
-        L = _lib.ransac_lib()
-        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_last_error().decode()}")
-
-
-def _usable_mask(usable):
-    um = 0
-    for s in usable:
-        um |= 1 << int(s)
-    return um
 
 
 def sample_scenes(sc: Scenes, n_hyp: int, seeds=None, want_idx: bool = False):
@@ -209,26 +163,14 @@ def sample_scenes(sc: Scenes, n_hyp: int, seeds=None, want_idx: bool = False):
     want_idx, idx [F*n_hyp,4] int32 (indices within the scene)."""
     _require_gpu()
     _chk_scenes(sc)
-    H, dev = int(n_hyp), sc.device
+    H = int(n_hyp)
     if H < 0:
         raise ValueError("n_hyp must not be negative")
-    if seeds is None:
-        if sc.seeds is None:
-            raise ValueError("no seeds: give them here or to pack_scenes")
-        sd = sc.seeds
-    else:
-        seeds = [int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds]
-        if len(seeds) != sc.F:
-            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
-        sd = torch.as_tensor(_np.array(seeds, dtype=_np.uint64).view(_np.int64)).to(dev)
-    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
-    n = sc.F * H
-    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
-    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
-    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
-    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
-    _call(sc, "cvxpnpl_ransac_sample_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(sc.x), _ptr(sc.X), _ptr(sc.K) if sc.per_scene_K else None,
-          _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    # (the words before their number is checked: this sampler has always taken an iterable without a len())
+    sd = _seeds_dev(sc, seeds if seeds is None else _seed_words(seeds))
+    p2, p3, Kh, idx = _sample_outputs(sc.F * H, sc, want_idx)
+    _call("ransac", sc, "cvxpnpl_ransac_sample_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(sc.x), _ptr(sc.X),
+          _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
     return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
 
 
@@ -236,15 +178,9 @@ def score_scenes(sc: Scenes, R, t, thresh: float = 2.0, status=None, usable=(0, 
     """cvxpnpl_ransac_score_scenes: count [F*H] int32, the inliers of hypothesis (f, h) = (R, t)[f*H + h] among scene f's correspondences."""
     _require_gpu()
     _chk_scenes(sc)
-    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F:
-        raise ValueError("R must be [F*H,3,3]")
-    n = R.shape[0]
-    _chk(R, "R", torch.float64, (n, 3, 3), sc.device)
-    _chk(t, "t", torch.float64, (n, 3), sc.device)
-    if status is not None:
-        _chk(status, "status", torch.int32, (n,), sc.device)
-    count = torch.empty((n,), dtype=torch.int32, device=sc.device)
-    _call(sc, "cvxpnpl_ransac_score_scenes", sc.F, n // sc.F, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable), _ptr(sc.K),
+    H = _poses(sc, R, t, status, None, sc.F, "R must be [F*H,3,3]", min_one=False)
+    count = torch.empty((sc.F * H,), dtype=torch.int32, device=sc.device)
+    _call("ransac", sc, "cvxpnpl_ransac_score_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable), _ptr(sc.K),
           sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(count))
     return count
 
@@ -254,18 +190,12 @@ def select_scenes(sc: Scenes, count, R, t, status, thresh: float = 2.0):
     head [F,4] int32 = (status, inliers, index within the scene, certified hypotheses), mask [total] uint8.  No synchronisation."""
     _require_gpu()
     _chk_scenes(sc)
-    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F or R.shape[0] < sc.F:
-        raise ValueError("R must be [F*H,3,3] with H >= 1")
-    n, dev = R.shape[0], sc.device
-    _chk(R, "R", torch.float64, (n, 3, 3), dev)
-    _chk(t, "t", torch.float64, (n, 3), dev)
-    _chk(status, "status", torch.int32, (n,), dev)
-    _chk(count, "count", torch.int32, (n,), dev)
+    H, dev = _poses(sc, R, t, status, count, sc.F, "R must be [F*H,3,3] with H >= 1", required=True), sc.device
     oR = torch.empty((sc.F, 3, 3), dtype=torch.float64, device=dev)
     ot = torch.empty((sc.F, 3), dtype=torch.float64, device=dev)
     head = torch.empty((sc.F, 4), dtype=torch.int32, device=dev)
     mask = torch.empty((sc.total,), dtype=torch.uint8, device=dev)
-    _call(sc, "cvxpnpl_ransac_select_scenes", sc.F, n // sc.F, _ptr(sc.offsets), sc.total, _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
+    _call("ransac", sc, "cvxpnpl_ransac_select_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
           sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(oR), _ptr(ot), _ptr(head), _ptr(mask))
     return oR, ot, head, mask
 
@@ -280,7 +210,7 @@ def assemble_consensus(sc: Scenes, mask):
     Bt = torch.empty((sc.F, 27), dtype=torch.float64, device=dev)
     Qt = torch.empty((sc.F, 45), dtype=torch.float64, device=dev)
     cnt = torch.empty((sc.F,), dtype=torch.int32, device=dev)
-    _call(sc, "cvxpnpl_ransac_assemble_consensus", sc.F, _ptr(sc.offsets), sc.total, _ptr(sc.x), _ptr(sc.X), _ptr(mask), _ptr(sc.K), sc.per_scene_K,
+    _call("ransac", sc, "cvxpnpl_ransac_assemble_consensus", sc.F, _ptr(sc.offsets), sc.total, _ptr(sc.x), _ptr(sc.X), _ptr(mask), _ptr(sc.K), sc.per_scene_K,
           _ptr(Bt), _ptr(Qt), _ptr(cnt))
     return Bt, Qt, cnt
 
@@ -290,17 +220,10 @@ def refit_update_scenes(sc: Scenes, fit, fit_count, thresh, R, t, head, mask):
     place -- when it is usable and keeps at least head[f,1] inliers.  One launch, no synchronisation."""
     _require_gpu()
     _chk_scenes(sc)
-    dev = sc.device
-    _chk(fit.R, "fit.R", torch.float64, (sc.F, 3, 3), dev)
-    _chk(fit.t, "fit.t", torch.float64, (sc.F, 3), dev)
-    _chk(fit.status, "fit.status", torch.int32, (sc.F,), dev)
-    _chk(fit_count, "fit_count", torch.int32, (sc.F,), dev)
-    _chk(R, "R", torch.float64, (sc.F, 3, 3), dev)
-    _chk(t, "t", torch.float64, (sc.F, 3), dev)
-    _chk(head, "head", torch.int32, (sc.F, 4), dev)
+    dev = _chk_refit(sc, fit, fit_count, R, t, head)
     _chk(mask, "mask", torch.uint8, (sc.total,), dev)
-    _call(sc, "cvxpnpl_ransac_refit_update_scenes", sc.F, _ptr(sc.offsets), sc.total, _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count), _ptr(sc.K),
-          sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask))
+    _call("ransac", sc, "cvxpnpl_ransac_refit_update_scenes", sc.F, _ptr(sc.offsets), sc.total, _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count),
+          _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask))
 
 
 # ---- a hypothesis budget per scene, solved in rounds (include/cvxpnpl_amd_ransac_adaptive.h, DESIGN.md section 19) ----------------------
@@ -344,48 +267,12 @@ def _check_adaptive(confidence, round_hyp):
     return c, int(round_hyp)
 
 
-def _call_adaptive(sc: Scenes, name, *args):
-    with torch.cuda.device(sc.device):
-        L = _lib.ransac_adaptive_lib()
-        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_adaptive_last_error().decode()}")
-
-
-def _chk_active(sc: Scenes, active, n_active):
-    """active: int32 on the scenes' device, one dimension, at least n_active entries (the kernels read the first n_active)."""
-    A = int(n_active)
-    if A < 0:
-        raise ValueError("n_active must not be negative")
-    if not isinstance(active, torch.Tensor) or active.dim() != 1 or active.shape[0] < A:
-        raise ValueError(f"active must be a tensor of at least n_active = {A} entries")
-    _chk(active, "active", torch.int32, (active.shape[0],), sc.device)
-    return A
-
-
-def _chk_budget(hyp0, n_round, cap):
-    h0, Hr, cp = int(hyp0), int(n_round), int(cap)
-    if h0 < 0 or Hr < 0 or cp < 0 or h0 + Hr > cp:
-        raise ValueError(f"a round needs 0 <= hyp0, 0 <= n_round and hyp0 + n_round <= cap, got {h0}, {Hr}, {cp}")
-    return h0, Hr, cp
-
-
-def _chk_state(sc: Scenes, st: AdaptiveState):
-    dev, i32 = sc.device, torch.int32
-    for name, shape, dt in (("active", (sc.F,), i32), ("active_next", (sc.F,), i32), ("done", (sc.F,), i32), ("n_active", (1,), i32),
-                            ("head", (sc.F, 4), i32), ("best", (sc.F,), i32), ("hyp_used", (sc.F,), i32), ("R", (sc.F, 3, 3), torch.float64),
-                            ("t", (sc.F, 3), torch.float64), ("mask", (sc.total,), torch.uint8)):
-        _chk(getattr(st, name), "state." + name, dt, shape, dev)
-    if st.active.data_ptr() == st.active_next.data_ptr():
-        raise ValueError("state.active and state.active_next are the same buffer")
-
-
 def adaptive_init(sc: Scenes) -> AdaptiveState:
     """cvxpnpl_ransac_adaptive_init: the state of a call, every scene active, nothing drawn (head[f] = (3, -1, 0, 0), best[f] = -1)."""
     _require_gpu()
     _chk_scenes(sc)
     st = AdaptiveState(sc.F, sc.total, sc.device)
-    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_init", sc.F, _ptr(st.active), _ptr(st.n_active), _ptr(st.head), _ptr(st.best), _ptr(st.hyp_used))
+    _call("ransac_adaptive", sc, "cvxpnpl_ransac_adaptive_init", sc.F, _ptr(st.active), _ptr(st.n_active), _ptr(st.head), _ptr(st.best), _ptr(st.hyp_used))
     return st
 
 
@@ -395,41 +282,13 @@ def sample_active(sc: Scenes, active, n_active: int, hyp0: int, n_round: int, ca
     [A*n_round,3,3] or None) and, with want_idx, idx [A*n_round,4] int32.  An entry outside [0, F) leaves its rows unwritten."""
     _require_gpu()
     _chk_scenes(sc)
-    A, dev = _chk_active(sc, active, n_active), sc.device
+    A = _chk_active(sc, active, n_active)
     h0, Hr, cp = _chk_budget(hyp0, n_round, cap)
-    if seeds is None:
-        if sc.seeds is None:
-            raise ValueError("no seeds: give them here or to pack_scenes")
-        sd = sc.seeds
-    else:
-        if len(seeds) != sc.F:
-            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
-        sd = torch.as_tensor(_seed_words(seeds)).to(dev)
-    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
-    n = A * Hr
-    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
-    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
-    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
-    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
-    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_sample", sc.F, A, _ptr(active), h0, Hr, cp, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(sc.x), _ptr(sc.X),
-                   _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    sd = _seeds_dev(sc, seeds)
+    p2, p3, Kh, idx = _sample_outputs(A * Hr, sc, want_idx)
+    _call("ransac_adaptive", sc, "cvxpnpl_ransac_adaptive_sample", sc.F, A, _ptr(active), h0, Hr, cp, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(sc.x),
+          _ptr(sc.X), _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
     return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
-
-
-def _chk_round(sc, A, R, t, status, count=None):
-    """The poses of a round: R [A*n_round,3,3] with n_round >= 1, and t, status, count of that length.  Returns n_round."""
-    if A < 1:
-        return 0
-    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % A or R.shape[0] < A:
-        raise ValueError("R must be [n_active*n_round,3,3] with n_round >= 1")
-    n = R.shape[0]
-    _chk(R, "R", torch.float64, (n, 3, 3), sc.device)
-    _chk(t, "t", torch.float64, (n, 3), sc.device)
-    if status is not None:
-        _chk(status, "status", torch.int32, (n,), sc.device)
-    if count is not None:
-        _chk(count, "count", torch.int32, (n,), sc.device)
-    return n // A
 
 
 def score_active(sc: Scenes, active, n_active: int, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
@@ -440,8 +299,8 @@ def score_active(sc: Scenes, active, n_active: int, R, t, thresh: float = 2.0, s
     A = _chk_active(sc, active, n_active)
     Hr = _chk_round(sc, A, R, t, status)
     count = torch.empty((A * Hr,), dtype=torch.int32, device=sc.device)
-    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_score", sc.F, A, _ptr(active), Hr, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status),
-                   _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(count))
+    _call("ransac_adaptive", sc, "cvxpnpl_ransac_adaptive_score", sc.F, A, _ptr(active), Hr, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status),
+          _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(count))
     return count
 
 
@@ -458,9 +317,9 @@ def update_active(sc: Scenes, st: AdaptiveState, n_active: int, hyp0: int, cap: 
         raise ValueError("status is required")
     Hr = _chk_round(sc, A, R, t, status, count)
     h0, Hr, cp = _chk_budget(hyp0, Hr, cap)
-    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, _ptr(sc.offsets), sc.total, _ptr(count), _ptr(R),
-                   _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
-                   _ptr(st.best), _ptr(st.mask), _ptr(st.hyp_used), _ptr(st.done))
+    _call("ransac_adaptive", sc, "cvxpnpl_ransac_adaptive_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, _ptr(sc.offsets), sc.total, _ptr(count), _ptr(R),
+          _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+          _ptr(st.best), _ptr(st.mask), _ptr(st.hyp_used), _ptr(st.done))
 
 
 def compact_active(sc: Scenes, st: AdaptiveState, n_active: int):
@@ -470,27 +329,13 @@ def compact_active(sc: Scenes, st: AdaptiveState, n_active: int):
     _chk_scenes(sc)
     _chk_state(sc, st)
     A = _chk_active(sc, st.active, n_active)
-    _call_adaptive(sc, "cvxpnpl_ransac_adaptive_compact", sc.F, A, _ptr(st.active), _ptr(st.done), _ptr(st.active_next), _ptr(st.n_active))
+    _call("ransac_adaptive", sc, "cvxpnpl_ransac_adaptive_compact", sc.F, A, _ptr(st.active), _ptr(st.done), _ptr(st.active_next), _ptr(st.n_active))
 
 
 # ---- guided sampling: the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h) ----------------
 # ransac_pnp_batch(quality=...) ranks every scene's correspondences by a matcher's score once per call and draws hypothesis h from the
 # n(h) best of them; the pool grows with h (the growth function of PROSAC) and is the whole scene from h = pool_full on, where the draw is
 # the uniform one again.  The kernels are those of libcvxpnpl_amd_ransac_guided.so; the stage wrappers below check every tensor as _chk does.
-
-
-def _call_guided(sc: Scenes, name, *args):
-    with torch.cuda.device(sc.device):
-        L = _lib.ransac_guided_lib()
-        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_guided_last_error().decode()}")
-
-
-def _chk_pool_full(pool_full):
-    if isinstance(pool_full, bool) or not isinstance(pool_full, (int, _np.integer)) or not 0 <= int(pool_full) <= 0x7FFFFFFF:
-        raise ValueError(f"pool_full must be an int >= 0 (and below 2^31), got {pool_full!r}")
-    return int(pool_full)
 
 
 def pool_size(h: int, n_corr: int, pool_full: int) -> int:
@@ -503,18 +348,6 @@ def pool_size(h: int, n_corr: int, pool_full: int) -> int:
     return int(_lib.ransac_guided_lib().cvxpnpl_ransac_guided_pool_host(h, m, pf))
 
 
-def _seeds_dev(sc: Scenes, seeds):
-    if seeds is None:
-        if sc.seeds is None:
-            raise ValueError("no seeds: give them here or to pack_scenes")
-        sd = sc.seeds
-    else:
-        if len(seeds) != sc.F:
-            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
-        sd = torch.as_tensor(_seed_words(seeds)).to(sc.device)
-    return _chk(sd, "seeds", torch.int64, (sc.F,), sc.device)
-
-
 def rank_scenes(sc: Scenes, quality):
     """cvxpnpl_ransac_guided_rank: order [total] int32 from quality [total] float64 (higher is better) on the scenes' device.  Scene f's
     slice of order is a permutation of 0 .. M_f - 1, best first: j before m when its quality is greater, or equal with j < m; a NaN counts
@@ -523,7 +356,7 @@ def rank_scenes(sc: Scenes, quality):
     _chk_scenes(sc)
     _chk(quality, "quality", torch.float64, (sc.total,), sc.device)
     order = torch.empty((sc.total,), dtype=torch.int32, device=sc.device)
-    _call_guided(sc, "cvxpnpl_ransac_guided_rank", sc.F, _ptr(sc.offsets), sc.total, max(sc.sizes), _ptr(quality), _ptr(order))
+    _call("ransac_guided", sc, "cvxpnpl_ransac_guided_rank", sc.F, _ptr(sc.offsets), sc.total, max(sc.sizes), _ptr(quality), _ptr(order))
     return order
 
 
@@ -538,13 +371,9 @@ def sample_scenes_guided(sc: Scenes, n_hyp: int, order, pool_full: int, seeds=No
         raise ValueError("n_hyp must not be negative")
     _chk(order, "order", torch.int32, (sc.total,), dev)
     sd = _seeds_dev(sc, seeds)
-    n = sc.F * H
-    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
-    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
-    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
-    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
-    _call_guided(sc, "cvxpnpl_ransac_guided_sample", sc.F, H, pf, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(order), _ptr(sc.x), _ptr(sc.X),
-                 _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    p2, p3, Kh, idx = _sample_outputs(sc.F * H, sc, want_idx)
+    _call("ransac_guided", sc, "cvxpnpl_ransac_guided_sample", sc.F, H, pf, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(order), _ptr(sc.x), _ptr(sc.X),
+          _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
     return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
 
 
@@ -559,13 +388,9 @@ def sample_active_guided(sc: Scenes, active, n_active: int, hyp0: int, n_round: 
     h0, Hr, cp = _chk_budget(hyp0, n_round, cap)
     _chk(order, "order", torch.int32, (sc.total,), dev)
     sd = _seeds_dev(sc, seeds)
-    n = A * Hr
-    p2 = torch.empty((n, 4, 2), dtype=torch.float64, device=dev)
-    p3 = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
-    Kh = torch.empty((n, 3, 3), dtype=torch.float64, device=dev) if sc.per_scene_K else None
-    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
-    _call_guided(sc, "cvxpnpl_ransac_guided_sample_active", sc.F, A, _ptr(active), h0, Hr, cp, pf, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(order),
-                 _ptr(sc.x), _ptr(sc.X), _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
+    p2, p3, Kh, idx = _sample_outputs(A * Hr, sc, want_idx)
+    _call("ransac_guided", sc, "cvxpnpl_ransac_guided_sample_active", sc.F, A, _ptr(active), h0, Hr, cp, pf, _ptr(sc.offsets), sc.total, _ptr(sd), _ptr(order),
+          _ptr(sc.x), _ptr(sc.X), _ptr(sc.K) if sc.per_scene_K else None, _ptr(idx), _ptr(p2), _ptr(p3), _ptr(Kh))
     return (p2, p3, Kh, idx) if want_idx else (p2, p3, Kh)
 
 
@@ -594,27 +419,38 @@ def _check_quality(quality, pool_full, szs, packed, n_hyp):
     return int(n_hyp) if pool_full is None else _chk_pool_full(pool_full)
 
 
-def _adaptive_rounds(sc, cap, conf, round_hyp, thresh, eps, max_iters, solver_opts, guided=None):
-    """The rounds of ransac_pnp_batch(confidence=...): returns the state and the number of rounds.  One 4-byte read-back per round -- the
-    number of scenes still active, which the next round's solve needs as a host number (its batch size).  guided: (order, pool_full),
-    the round's minimal sets then come from sample_active_guided."""
-    st = adaptive_init(sc)
+# ---- what the two batch calls share: the first checks, the rounds of an adaptive call, and everything after the winners are known --------
+
+def _batch_head(F, seed, n_hyp, confidence, round_hyp):
+    """The first checks of a batch call after its scenes, in this order (nothing here needs a GPU): the adaptive keywords, the seeds,
+    n_hyp.  Returns (seeds, confidence or None, round_hyp)."""
+    conf = None
+    if confidence is not None:
+        conf, round_hyp = _check_adaptive(confidence, round_hyp)
+    seeds = _resolve_seeds(seed, F)
+    if int(n_hyp) < 1:
+        raise ValueError("n_hyp must be at least 1")
+    return seeds, conf, round_hyp
+
+
+def _rounds(sc, st, stages, cap, conf, round_hyp, thresh):
+    """The rounds of a batch call with confidence=... over the state st (adaptive_init / adaptive_pnpl_init): returns their number.
+    stages: what differs between the scene kinds -- solve(active, n_active, hyp0, n_round), which draws the round's minimal sets and
+    solves them, and the kind's score_*_active and update_*_active.  One 4-byte read-back per round -- the number of scenes still active,
+    which the next round's solve needs as a host number (its batch size)."""
+    solve, score, update = stages
     A, h0, rounds = sc.F, 0, 0
     while A > 0 and h0 < cap:
         Hr = min(round_hyp, cap - h0)
-        if guided is None:
-            p2, p3, Kh = sample_active(sc, st.active, A, h0, Hr, cap)
-        else:
-            p2, p3, Kh = sample_active_guided(sc, st.active, A, h0, Hr, cap, guided[0], guided[1])
-        res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
-        count = score_active(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
-        update_active(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
+        res = solve(st.active, A, h0, Hr)
+        count = score(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+        update(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
         compact_active(sc, st, A)
         A = int(st.n_active.cpu()[0])   # the round's one synchronisation
         st.swap()
         h0 += Hr
         rounds += 1
-    return st, rounds
+    return rounds
 
 
 class _Fit:
@@ -624,21 +460,46 @@ class _Fit:
         self.R, self.t, self.status = R, t, status
 
 
-def _polish(sc, R, t, head, mask_pts, mask_lines, thresh):
+def _polish(sc, refit_update, R, t, head, masks, thresh):
     """The last step of the two batch calls with polish=True: one refine_scenes launch over the consensus masks, then
     the scenes' refit_update kernel, which takes the polished pose -- with its masks and count -- only when it keeps at least the consensus
     it was fitted to.  Its candidate status is the scene's own solve status when the refinement ended CONVERGED or MAXITER, and 3 (never
     taken) otherwise.  No synchronisation.  Returns the "refine" entry of the result."""
     from .refine import refine_scenes
 
-    res = refine_scenes(sc, R, t, mask_pts=mask_pts, mask_lines=mask_lines, status=head[:, 0])
+    res = refine_scenes(sc, R, t, mask_pts=masks[0], mask_lines=masks[1] if len(masks) > 1 else None, status=head[:, 0])
     fit = _Fit(res.R, res.t, torch.where(res.status <= 1, head[:, 0], torch.full_like(res.status, 3)))
-    cnt = head[:, 1].contiguous()
-    if mask_lines is None:
-        refit_update_scenes(sc, fit, cnt, thresh, R, t, head, mask_pts)
-    else:
-        refit_update_pnpl_scenes(sc, fit, cnt, thresh, R, t, head, mask_pts, mask_lines)
+    refit_update(sc, fit, head[:, 1].contiguous(), thresh, R, t, head, *masks)
     return {"cost": res.cost, "iters": res.iters, "status": res.status}
+
+
+def _finish(sc, kind, R, t, head, masks, thresh, refit, refit_rounds, polish, n_hyp, adaptive, pool_full):
+    """A batch call from the winners (R, t, head, masks) on: the refits of the consensus sets -- all scenes' in one solve at the cost seam
+    --, the polish, the call's one read-back and the result.  kind: the scene kind's (assemble_*_consensus, refit_update_*_scenes, the
+    result's names of the masks and of their offsets); adaptive: None or (state, rounds, confidence); pool_full: None for unguided draws."""
+    assemble, refit_update, names = kind
+    if refit:
+        for _ in range(max(1, int(refit_rounds))):
+            Bt, Qt, cnt = assemble(sc, *masks)
+            fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
+            refit_update(sc, fit, cnt, thresh, R, t, head, *masks)
+    refined = _polish(sc, refit_update, R, t, head, masks, thresh) if polish else None
+    h = head.cpu()   # the call's one synchronisation
+    out = {"R": R, "t": t}
+    for (mask_name, off_name), mask, off in zip(names, masks, (sc.offsets, getattr(sc, "line_offsets", None))):
+        out[mask_name], out[off_name] = mask.view(torch.bool), off
+    out.update(n_inliers=h[:, 1], status=h[:, 0], n_certified=h[:, 3], best_index=h[:, 2], head=h, sizes=sc.sizes)
+    if len(masks) > 1:
+        out["line_sizes"] = sc.line_sizes
+    out["n_hyp"] = int(n_hyp)
+    if polish:
+        out["refine"] = refined
+    if adaptive is not None:
+        state, rounds, conf = adaptive
+        out.update(hyp_used=state.hyp_used.cpu(), rounds=rounds, confidence=conf)
+    if pool_full is not None:
+        out["pool_full"] = pool_full
+    return out
 
 
 def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
@@ -666,19 +527,7 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     on, where the draws are the uniform ones again.  pool_full (an int >= 0) defaults to n_hyp; 0 is the uniform sampler.  With
     confidence the stopping rule is unchanged and counts inliers of the whole scene.  The result gains pool_full."""
     szs = _check_scenes(pts_2d, pts_3d, K, sizes)
-    F = len(szs)
-    if confidence is not None:
-        conf, round_hyp = _check_adaptive(confidence, round_hyp)
-    if seed is None:
-        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
-    if isinstance(seed, (int, _np.integer)):
-        seeds = [int(seed) + f for f in range(F)]
-    else:
-        seeds = [int(s) for s in seed]
-        if len(seeds) != F:
-            raise ValueError(f"{len(seeds)} seeds for {F} scenes")
-    if int(n_hyp) < 1:
-        raise ValueError("n_hyp must be at least 1")
+    seeds, conf, round_hyp = _batch_head(len(szs), seed, n_hyp, confidence, round_hyp)
     pool_full = _check_quality(quality, pool_full, szs, sizes is not None, n_hyp)
     sc = pack_scenes(pts_2d, pts_3d, K, sizes=szs if sizes is not None else None, device=device, seeds=seeds)
     guided = None
@@ -686,31 +535,26 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
         if sizes is not None and isinstance(quality, (list, tuple)):
             quality = _np.asarray(quality, dtype=_np.float64)
         guided = (rank_scenes(sc, _to_dev(quality, sc.device)), pool_full)
-    if confidence is not None:
-        state, rounds = _adaptive_rounds(sc, int(n_hyp), conf, round_hyp, thresh, eps, max_iters, solver_opts, guided)
+
+    def solve(p2, p3, Kh):  # the minimal solves of a fixed budget or of a round, in one launch sequence of the solver library
+        return pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+
+    adaptive = None
+    if conf is not None:
+        cap = int(n_hyp)
+        if guided is None:
+            stage = lambda act, A, h0, Hr: solve(*sample_active(sc, act, A, h0, Hr, cap))  # noqa: E731
+        else:
+            stage = lambda act, A, h0, Hr: solve(*sample_active_guided(sc, act, A, h0, Hr, cap, *guided))  # noqa: E731
+        state = adaptive_init(sc)
+        adaptive = (state, _rounds(sc, state, (stage, score_active, update_active), cap, conf, round_hyp, thresh), conf)
         R, t, head, mask = state.R, state.t, state.head, state.mask
-    else:
-        p2, p3, Kh = sample_scenes(sc, n_hyp) if guided is None else sample_scenes_guided(sc, n_hyp, guided[0], guided[1])
-        # no torch kernel from here to the read-back: the F * n_hyp minimal solves in one launch sequence of the solver library ...
-        res = pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+    else:  # no torch kernel from here to the read-back
+        res = solve(*(sample_scenes(sc, n_hyp) if guided is None else sample_scenes_guided(sc, n_hyp, *guided)))
         count = score_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
         R, t, head, mask = select_scenes(sc, count, res.R, res.t, res.status, thresh)
-    if refit:
-        for _ in range(max(1, int(refit_rounds))):  # ... and the F refits of the consensus sets in one solve at the cost seam
-            Bt, Qt, cnt = assemble_consensus(sc, mask)
-            fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
-            refit_update_scenes(sc, fit, cnt, thresh, R, t, head, mask)
-    refined = _polish(sc, R, t, head, mask, None, thresh) if polish else None
-    h = head.cpu()   # the call's one synchronisation
-    out = {"R": R, "t": t, "inliers": mask.view(torch.bool), "offsets": sc.offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3],
-           "best_index": h[:, 2], "head": h, "sizes": sc.sizes, "n_hyp": int(n_hyp)}
-    if polish:
-        out["refine"] = refined
-    if confidence is not None:
-        out.update(hyp_used=state.hyp_used.cpu(), rounds=rounds, confidence=conf)
-    if guided is not None:
-        out["pool_full"] = pool_full
-    return out
+    return _finish(sc, (assemble_consensus, refit_update_scenes, (("inliers", "offsets"),)), R, t, head, (mask,), thresh, refit, refit_rounds,
+                   polish, n_hyp, adaptive, pool_full)
 
 
 # ---- points AND lines, many scenes (include/cvxpnpl_amd_ransac_pnpl.h) --------------------------------------------
@@ -831,10 +675,6 @@ def _pack_half(a, tail, device):
     return a.to(device=device, dtype=torch.float64).reshape((-1,) + tail).contiguous()
 
 
-def _seed_words(seeds):
-    return _np.array([int(s) & 0xFFFFFFFFFFFFFFFF for s in seeds], dtype=_np.uint64).view(_np.int64)
-
-
 def pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=None, line_sizes=None, device=None, seeds=None) -> PnplScenes:
     """Validate (on the host) and pack a scene set of points and lines on the device; the argument order is pnpl's.  pts_2d / pts_3d: lists
     of F arrays [P_f,2] / [P_f,3], or packed with `sizes`; line_2d / line_3d: lists of F arrays [L_f,2,2] / [L_f,2,3], or packed with
@@ -858,35 +698,6 @@ def pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=None, line_sizes
                       _pack_half(line_3d, (2, 3), device), meta[:F + 1], meta[F + 1:2 * F + 2], ps, ls, _to_dev(Kd, device), sd)
 
 
-def _chk_pnpl_scenes(sc: PnplScenes):
-    dev = sc.device
-    if dev.type != "cuda":
-        raise ValueError(f"the scenes are on {dev}: cvxpnpl_amd has no CPU path")
-    _chk(sc.x, "scene pts_2d", torch.float64, (sc.total, 2), dev)
-    _chk(sc.X, "scene pts_3d", torch.float64, (sc.total, 3), dev)
-    _chk(sc.l2, "scene line_2d", torch.float64, (sc.line_total, 2, 2), dev)
-    _chk(sc.l3, "scene line_3d", torch.float64, (sc.line_total, 2, 3), dev)
-    _chk(sc.offsets, "offsets", torch.int64, (sc.F + 1,), dev)
-    _chk(sc.line_offsets, "line_offsets", torch.int64, (sc.F + 1,), dev)
-    _chk(sc.K, "K", torch.float64, (sc.F, 3, 3) if sc.per_scene_K else (3, 3), dev)
-
-
-def _scene_args(sc: PnplScenes):
-    return _ptr(sc.offsets), sc.total, _ptr(sc.line_offsets), sc.line_total
-
-
-def _data_args(sc: PnplScenes):
-    return _ptr(sc.x), _ptr(sc.X), _ptr(sc.l2), _ptr(sc.l3)
-
-
-def _call_pnpl(sc: PnplScenes, name, *args):
-    with torch.cuda.device(sc.device):
-        L = _lib.ransac_pnpl_lib()
-        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_pnpl_last_error().decode()}")
-
-
 def sample_assemble_scenes(sc: PnplScenes, n_hyp: int, seeds=None, want_idx: bool = False):
     """cvxpnpl_ransac_pnpl_sample_assemble: n_hyp minimal sets per scene, drawn over the union of the scene's points and lines (index c <
     P_f: point c; otherwise line c - P_f; scene f draws what synth.philox_minimal_sets(n_hyp, P_f + L_f, 4, seeds[f]) draws) and
@@ -897,21 +708,10 @@ def sample_assemble_scenes(sc: PnplScenes, n_hyp: int, seeds=None, want_idx: boo
     H, dev = int(n_hyp), sc.device
     if H < 0:
         raise ValueError("n_hyp must not be negative")
-    if seeds is None:
-        if sc.seeds is None:
-            raise ValueError("no seeds: give them here or to pack_pnpl_scenes")
-        sd = sc.seeds
-    else:
-        if len(seeds) != sc.F:
-            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
-        sd = torch.as_tensor(_seed_words(seeds)).to(dev)
-    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
-    n = sc.F * H
-    Qt = torch.empty((n, 45), dtype=torch.float64, device=dev)
-    Bt = torch.empty((n, 27), dtype=torch.float64, device=dev)
-    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
-    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_sample_assemble", sc.F, H, *_scene_args(sc), _ptr(sd), *_data_args(sc), _ptr(sc.K), sc.per_scene_K, _ptr(idx),
-               _ptr(Qt), _ptr(Bt))
+    sd = _seeds_dev(sc, seeds, "pack_pnpl_scenes")
+    Qt, Bt, idx = _cost_outputs(sc.F * H, dev, want_idx)
+    _call("ransac_pnpl", sc, "cvxpnpl_ransac_pnpl_sample_assemble", sc.F, H, *_scene_args(sc), _ptr(sd), *_data_args(sc), _ptr(sc.K), sc.per_scene_K, _ptr(idx),
+          _ptr(Qt), _ptr(Bt))
     return (Qt, Bt, idx) if want_idx else (Qt, Bt)
 
 
@@ -919,16 +719,10 @@ def score_pnpl_scenes(sc: PnplScenes, R, t, thresh: float = 2.0, status=None, us
     """cvxpnpl_ransac_pnpl_score: count [F*H] int32, the point plus line inliers of hypothesis (f, h) = (R, t)[f*H + h] in scene f."""
     _require_gpu()
     _chk_pnpl_scenes(sc)
-    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F:
-        raise ValueError("R must be [F*H,3,3]")
-    n = R.shape[0]
-    _chk(R, "R", torch.float64, (n, 3, 3), sc.device)
-    _chk(t, "t", torch.float64, (n, 3), sc.device)
-    if status is not None:
-        _chk(status, "status", torch.int32, (n,), sc.device)
-    count = torch.empty((n,), dtype=torch.int32, device=sc.device)
-    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_score", sc.F, n // sc.F, *_scene_args(sc), _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable), _ptr(sc.K),
-               sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(count))
+    H = _poses(sc, R, t, status, None, sc.F, "R must be [F*H,3,3]", min_one=False)
+    count = torch.empty((sc.F * H,), dtype=torch.int32, device=sc.device)
+    _call("ransac_pnpl", sc, "cvxpnpl_ransac_pnpl_score", sc.F, H, *_scene_args(sc), _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable), _ptr(sc.K),
+          sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(count))
     return count
 
 
@@ -938,20 +732,14 @@ def select_pnpl_scenes(sc: PnplScenes, count, R, t, status, thresh: float = 2.0)
     No synchronisation."""
     _require_gpu()
     _chk_pnpl_scenes(sc)
-    if not isinstance(R, torch.Tensor) or R.dim() != 3 or R.shape[0] % sc.F or R.shape[0] < sc.F:
-        raise ValueError("R must be [F*H,3,3] with H >= 1")
-    n, dev = R.shape[0], sc.device
-    _chk(R, "R", torch.float64, (n, 3, 3), dev)
-    _chk(t, "t", torch.float64, (n, 3), dev)
-    _chk(status, "status", torch.int32, (n,), dev)
-    _chk(count, "count", torch.int32, (n,), dev)
+    H, dev = _poses(sc, R, t, status, count, sc.F, "R must be [F*H,3,3] with H >= 1", required=True), sc.device
     oR = torch.empty((sc.F, 3, 3), dtype=torch.float64, device=dev)
     ot = torch.empty((sc.F, 3), dtype=torch.float64, device=dev)
     head = torch.empty((sc.F, 4), dtype=torch.int32, device=dev)
     mp = torch.empty((sc.total,), dtype=torch.uint8, device=dev)
     ml = torch.empty((sc.line_total,), dtype=torch.uint8, device=dev)
-    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_select", sc.F, n // sc.F, *_scene_args(sc), _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
-               sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(oR), _ptr(ot), _ptr(head), _ptr(mp), _ptr(ml))
+    _call("ransac_pnpl", sc, "cvxpnpl_ransac_pnpl_select", sc.F, H, *_scene_args(sc), _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
+          sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(oR), _ptr(ot), _ptr(head), _ptr(mp), _ptr(ml))
     return oR, ot, head, mp, ml
 
 
@@ -966,8 +754,8 @@ def assemble_pnpl_consensus(sc: PnplScenes, mask_pts, mask_lines):
     Bt = torch.empty((sc.F, 27), dtype=torch.float64, device=dev)
     Qt = torch.empty((sc.F, 45), dtype=torch.float64, device=dev)
     cnt = torch.empty((sc.F,), dtype=torch.int32, device=dev)
-    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_assemble_consensus", sc.F, *_scene_args(sc), *_data_args(sc), _ptr(mask_pts), _ptr(mask_lines), _ptr(sc.K),
-               sc.per_scene_K, _ptr(Bt), _ptr(Qt), _ptr(cnt))
+    _call("ransac_pnpl", sc, "cvxpnpl_ransac_pnpl_assemble_consensus", sc.F, *_scene_args(sc), *_data_args(sc), _ptr(mask_pts), _ptr(mask_lines), _ptr(sc.K),
+          sc.per_scene_K, _ptr(Bt), _ptr(Qt), _ptr(cnt))
     return Bt, Qt, cnt
 
 
@@ -976,18 +764,11 @@ def refit_update_pnpl_scenes(sc: PnplScenes, fit, fit_count, thresh, R, t, head,
     together, in place -- when it is usable and keeps at least head[f,1] inliers.  One launch, no synchronisation."""
     _require_gpu()
     _chk_pnpl_scenes(sc)
-    dev = sc.device
-    _chk(fit.R, "fit.R", torch.float64, (sc.F, 3, 3), dev)
-    _chk(fit.t, "fit.t", torch.float64, (sc.F, 3), dev)
-    _chk(fit.status, "fit.status", torch.int32, (sc.F,), dev)
-    _chk(fit_count, "fit_count", torch.int32, (sc.F,), dev)
-    _chk(R, "R", torch.float64, (sc.F, 3, 3), dev)
-    _chk(t, "t", torch.float64, (sc.F, 3), dev)
-    _chk(head, "head", torch.int32, (sc.F, 4), dev)
+    dev = _chk_refit(sc, fit, fit_count, R, t, head)
     _chk(mask_pts, "mask_pts", torch.uint8, (sc.total,), dev)
     _chk(mask_lines, "mask_lines", torch.uint8, (sc.line_total,), dev)
-    _call_pnpl(sc, "cvxpnpl_ransac_pnpl_refit_update", sc.F, *_scene_args(sc), _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count), _ptr(sc.K),
-               sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask_pts), _ptr(mask_lines))
+    _call("ransac_pnpl", sc, "cvxpnpl_ransac_pnpl_refit_update", sc.F, *_scene_args(sc), _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count),
+          _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask_pts), _ptr(mask_lines))
 
 
 # The cost seam does not tell the solver how many correspondences stand behind a cost, and its launch plan then assumes a well
@@ -1007,14 +788,6 @@ def solve_minimal_costs(Q45, B27, eps: float = 1e-6, max_iters: int = 100, devic
 # UNION of a scene's points and lines (index c < P_f: point c; otherwise line c - P_f; M_f = P_f + L_f).  The start of a call, the
 # compaction and the ranking are the ninth and tenth libraries', which know nothing of what a correspondence is; the three kernels that
 # touch points and lines are those of libcvxpnpl_amd_ransac_pnpl_adaptive.so.  The stage wrappers below check every tensor as _chk does.
-
-
-def _call_pnpl_adaptive(sc: PnplScenes, name, *args):
-    with torch.cuda.device(sc.device):
-        L = _lib.ransac_pnpl_adaptive_lib()
-        rc = getattr(L, name)(*args, _C.c_void_p(torch.cuda.current_stream(sc.device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {L.cvxpnpl_ransac_pnpl_adaptive_last_error().decode()}")
 
 
 def adaptive_pnpl_init(sc: PnplScenes) -> AdaptiveState:
@@ -1043,8 +816,8 @@ def rank_pnpl_scenes(sc: PnplScenes, quality, line_quality):
         _chk(line_quality, "line_quality", torch.float64, (sc.line_total,), dev)
         union[torch.as_tensor(_np.arange(sc.line_total) + _np.repeat(off_p[1:], sc.line_sizes)).to(dev)] = line_quality
     order = torch.empty((n,), dtype=torch.int32, device=dev)
-    _call_guided(sc, "cvxpnpl_ransac_guided_rank", sc.F, _ptr((sc.offsets + sc.line_offsets).contiguous()), n,
-                 max(p + l for p, l in zip(sc.sizes, sc.line_sizes)), _ptr(union), _ptr(order))
+    _call("ransac_guided", sc, "cvxpnpl_ransac_guided_rank", sc.F, _ptr((sc.offsets + sc.line_offsets).contiguous()), n,
+          max(p + l for p, l in zip(sc.sizes, sc.line_sizes)), _ptr(union), _ptr(order))
     return order
 
 
@@ -1065,21 +838,10 @@ def sample_assemble_active(sc: PnplScenes, active, n_active: int, hyp0: int, n_r
             raise ValueError("pool_full > 0 needs order (rank_pnpl_scenes)")
     else:
         _chk(order, "order", torch.int32, (sc.total + sc.line_total,), dev)
-    if seeds is None:
-        if sc.seeds is None:
-            raise ValueError("no seeds: give them here or to pack_pnpl_scenes")
-        sd = sc.seeds
-    else:
-        if len(seeds) != sc.F:
-            raise ValueError(f"{len(seeds)} seeds for {sc.F} scenes")
-        sd = torch.as_tensor(_seed_words(seeds)).to(dev)
-    _chk(sd, "seeds", torch.int64, (sc.F,), dev)
-    n = A * Hr
-    Qt = torch.empty((n, 45), dtype=torch.float64, device=dev)
-    Bt = torch.empty((n, 27), dtype=torch.float64, device=dev)
-    idx = torch.empty((n, 4), dtype=torch.int32, device=dev) if want_idx else None
-    _call_pnpl_adaptive(sc, "cvxpnpl_ransac_pnpl_adaptive_sample_assemble", sc.F, A, _ptr(active), h0, Hr, cp, pf, *_scene_args(sc), _ptr(sd), _ptr(order),
-                        *_data_args(sc), _ptr(sc.K), sc.per_scene_K, _ptr(idx), _ptr(Qt), _ptr(Bt))
+    sd = _seeds_dev(sc, seeds, "pack_pnpl_scenes")
+    Qt, Bt, idx = _cost_outputs(A * Hr, dev, want_idx)
+    _call("ransac_pnpl_adaptive", sc, "cvxpnpl_ransac_pnpl_adaptive_sample_assemble", sc.F, A, _ptr(active), h0, Hr, cp, pf, *_scene_args(sc), _ptr(sd),
+          _ptr(order), *_data_args(sc), _ptr(sc.K), sc.per_scene_K, _ptr(idx), _ptr(Qt), _ptr(Bt))
     return (Qt, Bt, idx) if want_idx else (Qt, Bt)
 
 
@@ -1091,8 +853,8 @@ def score_pnpl_active(sc: PnplScenes, active, n_active: int, R, t, thresh: float
     A = _chk_active(sc, active, n_active)
     Hr = _chk_round(sc, A, R, t, status)
     count = torch.empty((A * Hr,), dtype=torch.int32, device=sc.device)
-    _call_pnpl_adaptive(sc, "cvxpnpl_ransac_pnpl_adaptive_score", sc.F, A, _ptr(active), Hr, *_scene_args(sc), _ptr(R), _ptr(t), _ptr(status),
-                        _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(count))
+    _call("ransac_pnpl_adaptive", sc, "cvxpnpl_ransac_pnpl_adaptive_score", sc.F, A, _ptr(active), Hr, *_scene_args(sc), _ptr(R), _ptr(t), _ptr(status),
+          _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(count))
     return count
 
 
@@ -1111,9 +873,9 @@ def update_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, hyp0: i
         raise ValueError("status is required")
     Hr = _chk_round(sc, A, R, t, status, count)
     h0, Hr, cp = _chk_budget(hyp0, Hr, cap)
-    _call_pnpl_adaptive(sc, "cvxpnpl_ransac_pnpl_adaptive_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, *_scene_args(sc), _ptr(count), _ptr(R),
-                        _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
-                        _ptr(st.best), _ptr(st.mask), _ptr(st.mask_lines), _ptr(st.hyp_used), _ptr(st.done))
+    _call("ransac_pnpl_adaptive", sc, "cvxpnpl_ransac_pnpl_adaptive_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, *_scene_args(sc), _ptr(count), _ptr(R),
+          _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+          _ptr(st.best), _ptr(st.mask), _ptr(st.mask_lines), _ptr(st.hyp_used), _ptr(st.done))
 
 
 def _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, packed_p, packed_l, n_hyp):
@@ -1150,26 +912,6 @@ def _pack_quality(q, packed, device):
     return _to_dev(q, device).reshape(-1)
 
 
-def _adaptive_pnpl_rounds(sc, cap, conf, round_hyp, thresh, eps, max_iters, solver_opts, guided=None):
-    """The rounds of ransac_pnpl_batch(confidence=...): _adaptive_rounds with the minimal solves at the cost seam.  Returns the state and
-    the number of rounds; one 4-byte read-back per round.  guided: (order, pool_full)."""
-    st = adaptive_pnpl_init(sc)
-    order, pf = guided if guided is not None else (None, 0)
-    A, h0, rounds = sc.F, 0, 0
-    while A > 0 and h0 < cap:
-        Hr = min(round_hyp, cap - h0)
-        Qh, Bh = sample_assemble_active(sc, st.active, A, h0, Hr, cap, order, pf)
-        res = solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
-        count = score_pnpl_active(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
-        update_pnpl_active(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
-        compact_active(sc, st, A)
-        A = int(st.n_active.cpu()[0])   # the round's one synchronisation
-        st.swap()
-        h0 += Hr
-        rounds += 1
-    return st, rounds
-
-
 def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0,
                       refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, polish: bool = False,
                       confidence: Optional[float] = None, round_hyp: int = 64, quality=None, line_quality=None, pool_full: Optional[int] = None,
@@ -1201,53 +943,32 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
     gains pool_full."""
     ps, ls = _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes)
     F = len(ps)
-    if confidence is not None:
-        conf, round_hyp = _check_adaptive(confidence, round_hyp)
-    if seed is None:
-        seed = int(torch.randint(0, 2**31 - 1, (1,)).item())
-    if isinstance(seed, (int, _np.integer)):
-        seeds = [int(seed) + f for f in range(F)]
-    else:
-        seeds = [int(s) for s in seed]
-        if len(seeds) != F:
-            raise ValueError(f"{len(seeds)} seeds for {F} scenes")
-    if int(n_hyp) < 1:
-        raise ValueError("n_hyp must be at least 1")
+    seeds, conf, round_hyp = _batch_head(F, seed, n_hyp, confidence, round_hyp)
     pool_full = _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, sizes is not None, line_sizes is not None, n_hyp)
     sc = pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=sizes, line_sizes=line_sizes, device=device, seeds=seeds)
-    guided = None
+    order = None
     if pool_full is not None:  # the ranking of every scene's union: once per call, before the launch sequence
-        guided = (rank_pnpl_scenes(sc, _pack_quality(quality, sizes is not None, sc.device), _pack_quality(line_quality, line_sizes is not None, sc.device)),
-                  pool_full)
-    if confidence is not None:
-        state, rounds = _adaptive_pnpl_rounds(sc, int(n_hyp), conf, round_hyp, thresh, eps, max_iters, solver_opts, guided)
+        order = rank_pnpl_scenes(sc, _pack_quality(quality, sizes is not None, sc.device), _pack_quality(line_quality, line_sizes is not None, sc.device))
+
+    def solve(Qh, Bh):  # the minimal solves of a fixed budget or of a round, at the cost seam
+        return solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+
+    adaptive = None
+    if conf is not None:
+        cap = int(n_hyp)
+        stage = lambda act, A, h0, Hr: solve(*sample_assemble_active(sc, act, A, h0, Hr, cap, order, pool_full or 0))  # noqa: E731
+        state = adaptive_pnpl_init(sc)
+        adaptive = (state, _rounds(sc, state, (stage, score_pnpl_active, update_pnpl_active), cap, conf, round_hyp, thresh), conf)
         R, t, head, mp, ml = state.R, state.t, state.head, state.mask, state.mask_lines
-    else:
-        # no torch kernel from here to the read-back: draw + minimal assembly, the F * n_hyp minimal solves at the cost seam ...
-        if guided is None:
-            Qh, Bh = sample_assemble_scenes(sc, n_hyp)
+    else:  # no torch kernel from here to the read-back: draw + minimal assembly, the F * n_hyp minimal solves at the cost seam ...
+        if order is None:
+            res = solve(*sample_assemble_scenes(sc, n_hyp))
         else:  # the round sampler over the identity active list: problem f * n_hyp + h, the fixed layout
-            Qh, Bh = sample_assemble_active(sc, torch.arange(F, dtype=torch.int32, device=sc.device), F, 0, int(n_hyp), int(n_hyp), guided[0], guided[1])
-        res = solve_minimal_costs(Qh, Bh, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+            res = solve(*sample_assemble_active(sc, torch.arange(F, dtype=torch.int32, device=sc.device), F, 0, int(n_hyp), int(n_hyp), order, pool_full))
         count = score_pnpl_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
         R, t, head, mp, ml = select_pnpl_scenes(sc, count, res.R, res.t, res.status, thresh)
-    if refit:
-        for _ in range(max(1, int(refit_rounds))):  # ... and the F refits of the consensus sets in one more solve there
-            Bt, Qt, cnt = assemble_pnpl_consensus(sc, mp, ml)
-            fit = solve_cost_batch(Qt, Bt, eps=1e-9, max_iters=2500, device=sc.device)
-            refit_update_pnpl_scenes(sc, fit, cnt, thresh, R, t, head, mp, ml)
-    refined = _polish(sc, R, t, head, mp, ml, thresh) if polish else None
-    h = head.cpu()   # the call's one synchronisation
-    out = {"R": R, "t": t, "inliers_pts": mp.view(torch.bool), "offsets": sc.offsets, "inliers_lines": ml.view(torch.bool),
-           "line_offsets": sc.line_offsets, "n_inliers": h[:, 1], "status": h[:, 0], "n_certified": h[:, 3], "best_index": h[:, 2], "head": h,
-           "sizes": sc.sizes, "line_sizes": sc.line_sizes, "n_hyp": int(n_hyp)}
-    if polish:
-        out["refine"] = refined
-    if confidence is not None:
-        out.update(hyp_used=state.hyp_used.cpu(), rounds=rounds, confidence=conf)
-    if guided is not None:
-        out["pool_full"] = pool_full
-    return out
+    return _finish(sc, (assemble_pnpl_consensus, refit_update_pnpl_scenes, (("inliers_pts", "offsets"), ("inliers_lines", "line_offsets"))), R, t, head,
+                   (mp, ml), thresh, refit, refit_rounds, polish, n_hyp, adaptive, pool_full)
 
 
 def ransac_pnl_batch(line_2d, line_3d, K, **kw):
