@@ -86,7 +86,7 @@ REFINE_SRC = os.path.join(HERE, "csrc", "refine_hip.hip")
 REFINE_HOST_SRC = os.path.join(HERE, "csrc", "host_refine.cpp")
 REFINE_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine.so")
 REFINE_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine.resources.txt")
-REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"), os.path.join(HERE, "csrc", "refine_lanes.h"),
+REFINE_DEPS = [REFINE_SRC, REFINE_HOST_SRC, os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_kernel.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "refine_view.h"),
                os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine.h")]
@@ -102,7 +102,7 @@ REFINE_GRAD_HOST_SRC = os.path.join(HERE, "csrc", "host_refine_vjp.cpp")
 REFINE_GRAD_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine_grad.so")
 REFINE_GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_grad.resources.txt")
 REFINE_GRAD_DEPS = [REFINE_GRAD_SRC, REFINE_GRAD_HOST_SRC, os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_vjp_kernel.h"),
-                    os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                    os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "refine_view.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                     os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                     os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_grad.h")]
@@ -118,7 +118,7 @@ REFINE_ROBUST_HOST_SRC = os.path.join(HERE, "csrc", "host_refine_robust.cpp")
 REFINE_ROBUST_OUT = os.path.join(HERE, "libcvxpnpl_amd_refine_robust.so")
 REFINE_ROBUST_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_robust.resources.txt")
 REFINE_ROBUST_DEPS = [REFINE_ROBUST_SRC, REFINE_ROBUST_HOST_SRC, os.path.join(HERE, "csrc", "refine_robust_core.h"), os.path.join(HERE, "csrc", "refine_robust_kernel.h"),
-                      os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                      os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "refine_view.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                       os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                       os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                       os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust.h")]
@@ -136,7 +136,7 @@ REFINE_ROBUST_GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_refine_robust_
 REFINE_ROBUST_GRAD_DEPS = [REFINE_ROBUST_GRAD_SRC, REFINE_ROBUST_GRAD_HOST_SRC, os.path.join(HERE, "csrc", "refine_robust_vjp_core.h"),
                            os.path.join(HERE, "csrc", "refine_robust_vjp_kernel.h"), os.path.join(HERE, "csrc", "refine_robust_core.h"),
                            os.path.join(HERE, "csrc", "refine_robust_kernel.h"), os.path.join(HERE, "csrc", "refine_vjp_core.h"),
-                           os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                           os.path.join(HERE, "csrc", "refine_core.h"), os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "refine_view.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                            os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                            os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                            os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust_grad.h")]
@@ -199,7 +199,7 @@ REFINE_ROBUST_AUTO_DEPS = [REFINE_ROBUST_AUTO_SRC, REFINE_ROBUST_AUTO_HOST_SRC, 
                            os.path.join(HERE, "csrc", "refine_robust_auto_kernel.h"), os.path.join(HERE, "csrc", "refine_robust_vjp_core.h"),
                            os.path.join(HERE, "csrc", "refine_robust_core.h"), os.path.join(HERE, "csrc", "refine_robust_kernel.h"),
                            os.path.join(HERE, "csrc", "refine_vjp_core.h"), os.path.join(HERE, "csrc", "refine_core.h"),
-                           os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                           os.path.join(HERE, "csrc", "refine_lanes.h"), os.path.join(HERE, "csrc", "refine_view.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                            os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                            os.path.join(HERE, "csrc", "refine_entry.h"), ENTRY_ERROR_H, os.path.join(HERE, "csrc", "host_pool.h"),
                            os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_refine_robust.h"),

@@ -46,16 +46,16 @@ extern "C" int cvxpnpl_refine_batch_host(int64_t batch, int32_t n_p, const doubl
         for (int64_t b = lo; b < hi; ++b) {
             cvxr::HostLanes ln;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
-                                                            admit_mask, mask_pts, mask_lines, ln.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
+                                                   admit_mask, mask_pts, mask_lines, ln.pb, admit);
             cvxr::Result res;
-            cvxr::refine_problem(ln, pv.K, R + 9 * b, t + 3 * b, admit, o, res, cost + 2 * b);
+            cvxr::refine_problem(ln, Kb, R + 9 * b, t + 3 * b, admit, o, res, cost + 2 * b);
             const bool done = res.status <= cvxr::REFINE_MAXITER; // otherwise the input pose passes through bit for bit
             for (int i = 0; i < 9; ++i) R_out[9 * b + i] = done ? res.R[i] : R[9 * b + i];
             for (int i = 0; i < 3; ++i) t_out[3 * b + i] = done ? res.t[i] : t[3 * b + i];
             cost[2 * b + 1] = res.cost;
             iters[b] = res.iters; status_out[b] = res.status; n_live[b] = res.n_live;
-            if (cov) cvxr::covariance_problem(ln, pv.K, R_out + 9 * b, t_out + 3 * b, res.status, res.cost, res.n_live, o, cov + 36 * b);
+            if (cov) cvxr::covariance_problem(ln, Kb, R_out + 9 * b, t_out + 3 * b, res.status, res.cost, res.n_live, o, cov + 36 * b);
         }
     });
     return 0;

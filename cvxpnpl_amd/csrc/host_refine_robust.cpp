@@ -53,19 +53,19 @@ extern "C" int cvxpnpl_refine_robust_batch_host(int64_t batch, int32_t n_p, cons
             cvxrb::HostLanes ln;
             cvxrb::WProb &wp = ln.wp;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
-                                                            admit_mask, mask_pts, mask_lines, wp.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
+                                                   admit_mask, mask_pts, mask_lines, wp.pb, admit);
             cvxre::host_weights(wp, b, n_p, n_l, w_pts, w_lines);
             wp.ow_p = robust_w ? robust_w + b * ((int64_t)n_p + n_l) : nullptr;
             wp.ow_l = wp.ow_p ? wp.ow_p + n_p : nullptr;
             cvxrb::Result res;
-            cvxrb::robust_problem(ln, pv.K, R + 9 * b, t + 3 * b, admit, o, l, res, cost[2 * b]);
+            cvxrb::robust_problem(ln, Kb, R + 9 * b, t + 3 * b, admit, o, l, res, cost[2 * b]);
             const bool done = res.status <= cvxr::REFINE_MAXITER; // otherwise the input pose passes through bit for bit
             for (int i = 0; i < 9; ++i) R_out[9 * b + i] = done ? res.R[i] : R[9 * b + i];
             for (int i = 0; i < 3; ++i) t_out[3 * b + i] = done ? res.t[i] : t[3 * b + i];
             cost[2 * b + 1] = res.cost;
             iters[b] = res.iters; status_out[b] = res.status; n_live[b] = res.n_live;
-            n_inlier[b] = cvxrb::robust_weights_problem(ln, wp, pv.K, R_out + 9 * b, t_out + 3 * b, res.status, l);
+            n_inlier[b] = cvxrb::robust_weights_problem(ln, wp, Kb, R_out + 9 * b, t_out + 3 * b, res.status, l);
         }
     });
     return 0;

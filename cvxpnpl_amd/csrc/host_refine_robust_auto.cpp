@@ -68,13 +68,13 @@ extern "C" int cvxpnpl_robust_scale_batch_host(int64_t batch, int32_t n_p, const
         for (int64_t b = lo; b < hi; ++b) {
             cvxra::HostScaleLanes sl;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
-                                                            admit_mask, mask_pts, mask_lines, sl.wp.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
+                                                   admit_mask, mask_pts, mask_lines, sl.wp.pb, admit);
             cvxre::host_weights(sl.wp, b, n_p, n_l, w_pts, w_lines);
             sl.wp.ow_p = sq ? sq + b * ((int64_t)n_p + n_l) : nullptr;
             sl.wp.ow_l = sl.wp.ow_p ? sl.wp.ow_p + n_p : nullptr;
             cvxra::ScaleResult res;
-            cvxra::scale_problem(sl, pv.K, R + 9 * b, t + 3 * b, admit, res);
+            cvxra::scale_problem(sl, Kb, R + 9 * b, t + 3 * b, admit, res);
             sigma[b] = res.sigma; med_sq[b] = res.med_sq; n_live[b] = res.n_live; status_out[b] = res.status;
         }
     });
@@ -103,8 +103,8 @@ extern "C" int cvxpnpl_refine_robust_pp_batch_host(int64_t batch, int32_t n_p, c
             cvxra::PerProblemScale<cvxrb::HostLanes> ln;
             cvxrb::WProb &wp = ln.wp;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
-                                                            admit_mask, mask_pts, mask_lines, wp.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, status, status_stride,
+                                                   admit_mask, mask_pts, mask_lines, wp.pb, admit);
             cvxre::host_weights(wp, b, n_p, n_l, w_pts, w_lines);
             wp.ow_p = robust_w ? robust_w + b * ((int64_t)n_p + n_l) : nullptr;
             wp.ow_l = wp.ow_p ? wp.ow_p + n_p : nullptr;
@@ -112,13 +112,13 @@ extern "C" int cvxpnpl_refine_robust_pp_batch_host(int64_t batch, int32_t n_p, c
             ln.bad_scale = !cvxra::scale_usable(loss, scale);
             const cvxrb::Loss l = cvxrb::make_loss(loss, scale);
             cvxrb::Result res;
-            cvxrb::robust_problem(ln, pv.K, R + 9 * b, t + 3 * b, admit, o, l, res, cost[2 * b]);
+            cvxrb::robust_problem(ln, Kb, R + 9 * b, t + 3 * b, admit, o, l, res, cost[2 * b]);
             const bool done = res.status <= cvxr::REFINE_MAXITER; // otherwise the input pose passes through bit for bit
             for (int i = 0; i < 9; ++i) R_out[9 * b + i] = done ? res.R[i] : R[9 * b + i];
             for (int i = 0; i < 3; ++i) t_out[3 * b + i] = done ? res.t[i] : t[3 * b + i];
             cost[2 * b + 1] = res.cost;
             iters[b] = res.iters; status_out[b] = res.status; n_live[b] = res.n_live;
-            n_inlier[b] = cvxrb::robust_weights_problem(ln, wp, pv.K, R_out + 9 * b, t_out + 3 * b, res.status, l);
+            n_inlier[b] = cvxrb::robust_weights_problem(ln, wp, Kb, R_out + 9 * b, t_out + 3 * b, res.status, l);
         }
     });
     return 0;
@@ -140,14 +140,14 @@ extern "C" int cvxpnpl_robust_cov_batch_host(int64_t batch, int32_t n_p, const d
         for (int64_t b = lo; b < hi; ++b) {
             cvxrb::HostLanes ln;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, nullptr, 1, 0u, mask_pts, mask_lines,
-                                                            ln.wp.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, nullptr, 1, 0u, mask_pts, mask_lines,
+                                                   ln.wp.pb, admit);
             cvxre::host_weights(ln.wp, b, n_p, n_l, w_pts, w_lines);
             ln.wp.ow_p = ln.wp.ow_l = nullptr;
             const double scale = scale_each ? scale_each[b] : scale_px;
             const bool usable = cvxra::scale_usable(loss, scale);
             const bool diff = !status || status[b] == cvxr::REFINE_CONVERGED || status[b] == cvxr::REFINE_MAXITER;
-            cov_status[b] = cvxra::robust_cov_problem(ln, pv.K, R + 9 * b, t + 3 * b, diff, !usable, cvxrb::make_loss(loss, usable ? scale : 1.0), cov + 36 * b);
+            cov_status[b] = cvxra::robust_cov_problem(ln, Kb, R + 9 * b, t + 3 * b, diff, !usable, cvxrb::make_loss(loss, usable ? scale : 1.0), cov + 36 * b);
         }
     });
     return 0;

@@ -45,13 +45,13 @@ extern "C" int cvxpnpl_refine_robust_vjp_batch_host(int64_t batch, int32_t n_p, 
             cvxrb::HostLanes ln;
             cvxrb::WProb &wp = ln.wp;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, refine_status, status_stride,
-                                                            admit_mask, mask_pts, mask_lines, wp.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, refine_status, status_stride,
+                                                   admit_mask, mask_pts, mask_lines, wp.pb, admit);
             cvxre::host_weights(wp, b, n_p, n_l, w_pts, w_lines);
             wp.ow_p = cvxre::slice(g_w_pts, b, n_p); wp.ow_l = cvxre::slice(g_w_lines, b, n_l); // (the weights' gradients: refine_robust_vjp_core.h)
             cvxrg::Grads g;
             cvxre::host_grads(g, b, n_p, n_l, g_pts_2d, g_pts_3d, g_line_2d, g_line_3d);
-            vjp_status[b] = cvxrbg::robust_vjp_problem(ln, wp, pv.K, R + 9 * b, t + 3 * b, grad_R ? grad_R + 9 * b : nullptr,
+            vjp_status[b] = cvxrbg::robust_vjp_problem(ln, wp, Kb, R + 9 * b, t + 3 * b, grad_R ? grad_R + 9 * b : nullptr,
                                                        grad_t ? grad_t + 3 * b : nullptr, admit, true, l, g, info ? info + 2 * b : nullptr);
         }
     });

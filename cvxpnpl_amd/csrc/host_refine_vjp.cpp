@@ -39,11 +39,11 @@ extern "C" int cvxpnpl_refine_vjp_batch_host(int64_t batch, int32_t n_p, const d
         for (int64_t b = lo; b < hi; ++b) {
             cvxr::HostLanes ln;
             bool admit;
-            const cvx::ProblemView pv = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, refine_status, status_stride,
-                                                            admit_mask, mask_pts, mask_lines, ln.pb, admit);
+            const double *Kb = cvxre::host_problem(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, refine_status, status_stride,
+                                                   admit_mask, mask_pts, mask_lines, ln.pb, admit);
             cvxrg::Grads g;
             cvxre::host_grads(g, b, n_p, n_l, g_pts_2d, g_pts_3d, g_line_2d, g_line_3d);
-            vjp_status[b] = cvxrg::vjp_problem(ln, 0, 1, pv.K, R + 9 * b, t + 3 * b, grad_R ? grad_R + 9 * b : nullptr, grad_t ? grad_t + 3 * b : nullptr,
+            vjp_status[b] = cvxrg::vjp_problem(ln, 0, 1, Kb, R + 9 * b, t + 3 * b, grad_R ? grad_R + 9 * b : nullptr, grad_t ? grad_t + 3 * b : nullptr,
                                                admit, true, g, info ? info + 2 * b : nullptr);
         }
     });

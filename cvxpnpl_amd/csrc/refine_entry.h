@@ -14,6 +14,7 @@
 #include "entry_error.h"
 #include "host_pool.h"
 #include "refine_core.h"
+#include "refine_view.h"
 
 #define CVXRE_FN inline __attribute__((visibility("hidden")))
 
@@ -100,17 +101,14 @@ CVXRE_FN T *slice(T *p, int64_t b, int32_t n, int per = 1)
     return p && n > 0 ? p + b * n * per : nullptr;
 }
 
-// problem b of a host batch: its view (K and the correspondence slices), its Prob with the masks, and whether its status is admitted
-CVXRE_FN cvx::ProblemView host_problem(int64_t b, int32_t n_p, const double *pts_2d, const double *pts_3d, int32_t n_l, const double *line_2d,
-                                       const double *line_3d, const double *K, int32_t K_per_problem, const int32_t *status, int64_t status_stride,
-                                       uint32_t admit_mask, const uint8_t *mask_pts, const uint8_t *mask_lines, cvxr::Prob &pb, bool &admit)
+// problem b of a host batch: its Prob with the masks (refine_view.h's batch_prob, the statement the kernels use), whether its status is
+// admitted, and its K returned
+CVXRE_FN const double *host_problem(int64_t b, int32_t n_p, const double *pts_2d, const double *pts_3d, int32_t n_l, const double *line_2d,
+                                    const double *line_3d, const double *K, int32_t K_per_problem, const int32_t *status, int64_t status_stride,
+                                    uint32_t admit_mask, const uint8_t *mask_pts, const uint8_t *mask_lines, cvxr::Prob &pb, bool &admit)
 {
-    const cvx::ProblemView pv = cvx::make_view(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem);
-    pb.n_p = n_p; pb.n_l = n_l;
-    pb.p2 = pv.p2; pb.p3 = pv.p3; pb.l2 = pv.l2; pb.l3 = pv.l3;
-    pb.mp = slice(mask_pts, b, n_p); pb.ml = slice(mask_lines, b, n_l);
     admit = !status || cvxr::admitted(status[b * status_stride], admit_mask);
-    return pv;
+    return cvxr::batch_prob(b, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem, mask_pts, mask_lines, pb);
 }
 
 // ... its weights (W: cvxrb::WProb) and its gradient outputs (G: cvxrg::Grads)

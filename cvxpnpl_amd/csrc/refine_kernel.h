@@ -9,15 +9,15 @@
 //   refine_scenes_kernel       packed scenes (offsets, optional masks): ONE workgroup of 256 per scene, records re-read in every pass, the
 //       sums through a wavefront butterfly and LDS; every lane then holds the same totals and takes the same step.  Scenes of any size;
 //       a very large scene is still one workgroup.
-// Both clamp what they index: a group beyond the batch works on the last problem and writes nothing, a scene's slices go through
-// cvxn::scene_slice.
+// Both clamp what they index: a group beyond the batch works on the last problem and writes nothing, a scene's slices are clamped.  The
+// view of a problem or a scene, and the staging of its pose, are refine_view.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ransac_common.h"
 #include "refine_core.h"
 #include "refine_lanes.h"
+#include "refine_view.h"
 
 namespace cvxr {
 
@@ -56,16 +56,12 @@ __global__ void __launch_bounds__(TPB) refine_group_kernel(BatchArgs a)
     const int64_t b = mine ? g : a.batch - 1; // an empty group of the last wavefront shadows the last problem and writes nothing
     GroupLanes<RPL> ln;
     ln.lane = threadIdx.x & 15;
-    const cvx::ProblemView pv = cvx::make_view(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem);
-    ln.pb.n_p = a.n_p; ln.pb.n_l = a.n_l;
-    ln.pb.p2 = pv.p2; ln.pb.p3 = pv.p3; ln.pb.l2 = pv.l2; ln.pb.l3 = pv.l3;
-    ln.pb.mp = a.mp ? a.mp + b * a.n_p : nullptr;
-    ln.pb.ml = a.ml ? a.ml + b * a.n_l : nullptr;
+    const double *K = batch_prob(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem, a.mp, a.ml, ln.pb);
     ln.load();
     const bool admit = mine && (!a.status || admitted(a.status[b * a.status_stride], a.admit));
     const bool writer = mine && ln.lane == 0;
     Result res;
-    refine_problem(ln, pv.K, a.R + 9 * b, a.t + 3 * b, admit, a.opts, res, writer ? a.out.cost + 2 * b : nullptr);
+    refine_problem(ln, K, a.R + 9 * b, a.t + 3 * b, admit, a.opts, res, writer ? a.out.cost + 2 * b : nullptr);
     if (writer) write_result(a.out, b, res, a.R + 9 * b, a.t + 3 * b);
 }
 
@@ -76,12 +72,8 @@ __global__ void __launch_bounds__(TPB) cov_group_kernel(BatchArgs a)
     if (g >= a.batch) return; // whole groups: the exchanges stay inside a group
     GroupLanes<0> ln;
     ln.lane = threadIdx.x & 15;
-    const cvx::ProblemView pv = cvx::make_view(g, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem);
-    ln.pb.n_p = a.n_p; ln.pb.n_l = a.n_l;
-    ln.pb.p2 = pv.p2; ln.pb.p3 = pv.p3; ln.pb.l2 = pv.l2; ln.pb.l3 = pv.l3;
-    ln.pb.mp = a.mp ? a.mp + g * a.n_p : nullptr;
-    ln.pb.ml = a.ml ? a.ml + g * a.n_l : nullptr;
-    covariance_problem(ln, pv.K, a.out.R + 9 * g, a.out.t + 3 * g, a.out.status[g], a.out.cost[2 * g + 1], a.out.n_live[g], a.opts,
+    const double *K = batch_prob(g, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem, a.mp, a.ml, ln.pb);
+    covariance_problem(ln, K, a.out.R + 9 * g, a.out.t + 3 * g, a.out.status[g], a.out.cost[2 * g + 1], a.out.n_live[g], a.opts,
                        ln.lane == 0 ? a.out.cov + 36 * g : nullptr);
 }
 
@@ -98,30 +90,19 @@ struct SceneArgs {
     Outputs out;
 };
 
-// the workgroup's scene: both slices clamped, K / R / t staged in LDS (read from LDS they are per-lane values; read through a uniform pointer,
-// the pose and everything computed from it would crowd the scalar registers).  R, t: the poses to stage, [n_scenes][9] / [n_scenes][3].
+// the workgroup's scene: the poses R, t ([n_scenes][9] / [n_scenes][3]) staged in LDS with K, the scene's records into the lanes
 __device__ __forceinline__ void scene_lanes(const SceneArgs &a, int64_t f, const double *R, const double *t, double *red, double *pose, BlockLanes &ln)
 {
-    if (threadIdx.x < 9) pose[threadIdx.x] = a.K[(a.K_per_scene ? f * 9 : 0) + threadIdx.x];
-    else if (threadIdx.x < 18) pose[threadIdx.x] = R[9 * f + threadIdx.x - 9];
-    else if (threadIdx.x < 21) pose[threadIdx.x] = t[3 * f + threadIdx.x - 18];
-    __syncthreads();
-    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts);
-    cvxn::Slice sl{0, 0};
-    if (a.off_l) sl = cvxn::scene_slice(a.off_l, f, a.n_lines);
+    stage_pose(a.K, a.K_per_scene, R, t, f, pose, [] {});
+    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts), sl = line_slice(a.off_l, f, a.n_lines);
     ln.red = red;
-    ln.pb.n_p = sp.n;
-    ln.pb.n_l = sl.n > 0x7fffffff - sp.n ? 0x7fffffff - sp.n : sl.n;
-    ln.pb.p2 = a.p2 + sp.beg * 2; ln.pb.p3 = a.p3 + sp.beg * 3; // (never followed where the slice is empty)
-    ln.pb.l2 = a.l2 + sl.beg * 4; ln.pb.l3 = a.l3 + sl.beg * 6;
-    ln.pb.mp = a.mp ? a.mp + sp.beg : nullptr;
-    ln.pb.ml = a.ml ? a.ml + sl.beg : nullptr;
+    scene_prob(sp, sl, a.p2, a.p3, a.l2, a.l3, a.mp, a.ml, ln.pb);
 }
 
 __global__ void __launch_bounds__(TPB) refine_scenes_kernel(SceneArgs a)
 {
     __shared__ double red[(WAVES + 1) * ACC_N];
-    __shared__ double pose[21];
+    __shared__ double pose[POSE_N];
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return; // (workgroup-uniform)
     BlockLanes ln;
@@ -137,7 +118,7 @@ __global__ void __launch_bounds__(TPB) refine_scenes_kernel(SceneArgs a)
 __global__ void __launch_bounds__(TPB) cov_scenes_kernel(SceneArgs a)
 {
     __shared__ double red[(WAVES + 1) * ACC_N];
-    __shared__ double pose[21];
+    __shared__ double pose[POSE_N];
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return;
     BlockLanes ln;

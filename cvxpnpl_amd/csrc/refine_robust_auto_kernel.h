@@ -1,22 +1,25 @@
 // refine_robust_auto_kernel.h -- the device side of include/cvxpnpl_amd_refine_robust_auto.h; the mathematics is
 // refine_robust_auto_core.h, shared with the host path; the lanes, their exchanges and the argument blocks are refine_robust_kernel.h's
-// and refine_lanes.h's, included and not edited.
+// and refine_lanes.h's.
 //   robust_scale_group_kernel<RPL> / robust_scale_scenes_kernel     sigma per problem from the median of s_k.  16 lanes per problem with
 //       1, 2 or 4 records (and their s_k, through all 63 rounds) in a lane's registers, RPL = 0 beyond 64 records: s_k is read again from
 //       sq; one workgroup of 256 per scene, which reads sq again too.  A lane only ever reads back what it has written itself.
 //   refine_robust_pp_group_kernel<RPL> / refine_robust_pp_scenes_kernel, robust_w_pp_group_kernel / robust_w_pp_scenes_kernel
 //       refine_robust_kernel.h's kernels with the loss made from scale[b] (a null array: the uniform scale of the options).
 //   robust_cov_group_kernel / robust_cov_scenes_kernel               the sandwich covariance at a pose, a pass of its own.
-// All clamp what they index as refine_robust_kernel.h's do; whole groups beyond the batch leave where no wavefront vote follows.
+// All clamp what they index as refine_robust_kernel.h's do (through its batch_prob and scene_lanes, over refine_view.h); whole groups
+// beyond the batch leave where no wavefront vote follows.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "refine_robust_auto_core.h"
 #include "refine_robust_kernel.h"
+#include "refine_view.h"
 
 namespace cvxra {
 
+using cvxr::POSE_N;
 using cvxr::TPB;
 using cvxr::WAVES;
 
@@ -118,32 +121,6 @@ struct SelBlockLanes {
     __device__ __forceinline__ void sum(double *x) { w.template sum<N>(x); }
 };
 
-// the workgroup's scene: refine_robust_kernel.h's scene_lanes with the scale that goes to pose[21] given by the caller
-__device__ __forceinline__ void stage_scene(const cvxrb::SceneArgs &a, int64_t f, const double *R, const double *t, double scale, double *red, double *pose,
-                                            cvxrb::WBlockLanes &ln)
-{
-    if (threadIdx.x < 9) pose[threadIdx.x] = a.K[(a.K_per_scene ? f * 9 : 0) + threadIdx.x];
-    else if (threadIdx.x < 18) pose[threadIdx.x] = R[9 * f + threadIdx.x - 9];
-    else if (threadIdx.x < 21) pose[threadIdx.x] = t[3 * f + threadIdx.x - 18];
-    else if (threadIdx.x == 21) pose[21] = scale;
-    __syncthreads();
-    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts);
-    cvxn::Slice sl{0, 0};
-    if (a.off_l) sl = cvxn::scene_slice(a.off_l, f, a.n_lines);
-    ln.b.red = red;
-    cvxr::Prob &pb = ln.wp.pb;
-    pb.n_p = sp.n;
-    pb.n_l = sl.n > 0x7fffffff - sp.n ? 0x7fffffff - sp.n : sl.n;
-    pb.p2 = a.p2 + sp.beg * 2; pb.p3 = a.p3 + sp.beg * 3; // (never followed where the slice is empty)
-    pb.l2 = a.l2 + sl.beg * 4; pb.l3 = a.l3 + sl.beg * 6;
-    pb.mp = a.mp ? a.mp + sp.beg : nullptr;
-    pb.ml = a.ml ? a.ml + sl.beg : nullptr;
-    ln.wp.wp = cvxrb::in_vgpr(a.wp ? a.wp + sp.beg : nullptr);
-    ln.wp.wl = cvxrb::in_vgpr(a.wl ? a.wl + sl.beg : nullptr);
-    ln.wp.ow_p = a.out.rw_p ? a.out.rw_p + sp.beg : nullptr;
-    ln.wp.ow_l = a.out.rw_l ? a.out.rw_l + sl.beg : nullptr;
-}
-
 // ---- 1. the scale ----
 
 template <int RPL>
@@ -168,12 +145,12 @@ __global__ void __launch_bounds__(TPB) robust_scale_group_kernel(AutoBatchArgs p
 __global__ void __launch_bounds__(TPB) robust_scale_scenes_kernel(AutoSceneArgs pa)
 {
     __shared__ double red[(WAVES + 1) * cvxr::ACC_N];
-    __shared__ double pose[22];
+    __shared__ double pose[POSE_N + 1];
     const cvxrb::SceneArgs &a = pa.a;
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return; // (workgroup-uniform)
     SelBlockLanes sl;
-    stage_scene(a, f, a.R, a.t, 0.0, red, pose, sl.w);
+    cvxrb::scene_lanes(a, f, a.R, a.t, 0.0, red, pose, sl.w);
     const bool admit = !a.status || cvxr::admitted(a.status[f * a.status_stride], a.admit);
     const double *ps = pose;
     ScaleResult res;
@@ -184,7 +161,7 @@ __global__ void __launch_bounds__(TPB) robust_scale_scenes_kernel(AutoSceneArgs 
     }
 }
 
-// ---- 2. the loop at a scale per problem: refine_robust_kernel.h's kernels, line for line, with scale[b] ----
+// ---- 2. the loop at a scale per problem: refine_robust_kernel.h's kernels with scale[b] ----
 
 template <int RPL>
 __global__ void __launch_bounds__(TPB) refine_robust_pp_group_kernel(AutoBatchArgs pa)
@@ -225,33 +202,33 @@ __global__ void __launch_bounds__(TPB) robust_w_pp_group_kernel(AutoBatchArgs pa
 __global__ void __launch_bounds__(TPB) refine_robust_pp_scenes_kernel(AutoSceneArgs pa)
 {
     __shared__ double red[(WAVES + 1) * cvxr::ACC_N];
-    __shared__ double pose[22];
+    __shared__ double pose[POSE_N + 1];
     const cvxrb::SceneArgs &a = pa.a;
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return; // (workgroup-uniform)
     PerProblemScale<cvxrb::WBlockLanes> ln;
-    stage_scene(a, f, a.R, a.t, pa.scale ? pa.scale[f] : a.scale_px, red, pose, ln);
+    cvxrb::scene_lanes(a, f, a.R, a.t, pa.scale ? pa.scale[f] : a.scale_px, red, pose, ln);
     const bool admit = !a.status || cvxr::admitted(a.status[f * a.status_stride], a.admit);
     const cvxrb::LaneOutputs lo = cvxrb::lane_outputs<6>(a.out, f);
     cvxrb::Result res;
     double c0;
     const double *ps = pose;
-    ln.bad_scale = !scale_usable(a.loss_kind, ps[21]);
-    cvxrb::robust_problem(ln, ps, ps + 9, ps + 18, admit, a.opts, cvxrb::make_loss(a.loss_kind, ps[21]), res, c0);
+    ln.bad_scale = !scale_usable(a.loss_kind, ps[POSE_N]);
+    cvxrb::robust_problem(ln, ps, ps + 9, ps + 18, admit, a.opts, cvxrb::make_loss(a.loss_kind, ps[POSE_N]), res, c0);
     if (threadIdx.x == 0) cvxrb::write_result<true>(lo, res, c0, ps + 9, ps + 18);
 }
 
 __global__ void __launch_bounds__(TPB) robust_w_pp_scenes_kernel(AutoSceneArgs pa)
 {
     __shared__ double red[(WAVES + 1) * cvxr::ACC_N];
-    __shared__ double pose[22];
+    __shared__ double pose[POSE_N + 1];
     const cvxrb::SceneArgs &a = pa.a;
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return;
     cvxrb::WBlockLanes ln;
-    stage_scene(a, f, a.out.R, a.out.t, pa.scale ? pa.scale[f] : a.scale_px, red, pose, ln);
+    cvxrb::scene_lanes(a, f, a.out.R, a.out.t, pa.scale ? pa.scale[f] : a.scale_px, red, pose, ln);
     const double *ps = pose;
-    const int n = cvxrb::robust_weights_problem(ln, ln.wp, ps, ps + 9, ps + 18, a.out.status[f], cvxrb::make_loss(a.loss_kind, ps[21]));
+    const int n = cvxrb::robust_weights_problem(ln, ln.wp, ps, ps + 9, ps + 18, a.out.status[f], cvxrb::make_loss(a.loss_kind, ps[POSE_N]));
     if (threadIdx.x == 0) a.out.n_inlier[f] = n;
 }
 
@@ -283,15 +260,15 @@ __global__ void __launch_bounds__(TPB) robust_cov_group_kernel(AutoBatchArgs pa)
 __global__ void __launch_bounds__(TPB) robust_cov_scenes_kernel(AutoSceneArgs pa)
 {
     __shared__ double red[(WAVES + 1) * cvxr::ACC_N];
-    __shared__ double pose[22];
+    __shared__ double pose[POSE_N + 1];
     const cvxrb::SceneArgs &a = pa.a;
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return;
     cvxrb::WBlockLanes ln;
-    stage_scene(a, f, a.R, a.t, pa.scale ? pa.scale[f] : a.scale_px, red, pose, ln);
+    cvxrb::scene_lanes(a, f, a.R, a.t, pa.scale ? pa.scale[f] : a.scale_px, red, pose, ln);
     const double *ps = pose;
-    const bool usable = scale_usable(a.loss_kind, ps[21]);
-    const int st = robust_cov_problem(ln, ps, ps + 9, ps + 18, differentiated(a.status, f), !usable, cvxrb::make_loss(a.loss_kind, usable ? ps[21] : 1.0),
+    const bool usable = scale_usable(a.loss_kind, ps[POSE_N]);
+    const int st = robust_cov_problem(ln, ps, ps + 9, ps + 18, differentiated(a.status, f), !usable, cvxrb::make_loss(a.loss_kind, usable ? ps[POSE_N] : 1.0),
                                       threadIdx.x == 0 ? pa.cov + 36 * f : nullptr);
     if (threadIdx.x == 0) pa.cov_status[f] = st;
 }

@@ -2,20 +2,22 @@
 // the mathematics and the loop are refine_robust_core.h, shared with the host path; the lanes' exchanges are refine_lanes.h's.
 //   refine_robust_group_kernel<RPL>   the batch form: 16 lanes per problem, four problems per wavefront, no LDS, the wavefront vote of
 //       refine_group_kernel.  A lane's register copy of a record is refine_lanes.h's Rec plus its weight.
-//   refine_robust_scenes_kernel       packed scenes: one workgroup of 256 per scene, slices through cvxn::scene_slice.
+//   refine_robust_scenes_kernel       packed scenes: one workgroup of 256 per scene.
 //   robust_w_group_kernel / robust_w_scenes_kernel   rho'(s_k) per record and the inlier count at the returned pose: a pass of its own on the
 //       same stream after the loop kernel (as the covariance of refine_kernel.h is), re-reading the records.
-// All clamp what they index: a group beyond the batch works on the last problem and writes nothing, a scene's slices are clamped.
+// All clamp what they index: a group beyond the batch works on the last problem and writes nothing, a scene's slices are clamped.  The
+// view of a problem or a scene, and the staging of its pose, are refine_view.h's; this header adds the weights and the per-record output.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include "ransac_common.h"
 #include "refine_lanes.h"
 #include "refine_robust_core.h"
+#include "refine_view.h"
 
 namespace cvxrb {
 
+using cvxr::POSE_N;
 using cvxr::TPB;
 using cvxr::WAVES;
 
@@ -138,19 +140,23 @@ struct BatchArgs {
     Outputs out;
 };
 
-// problem b of the batch form
-__device__ __forceinline__ const double *batch_prob(const BatchArgs &a, int64_t b, WProb &wp)
+// problem b of a batch form with weights: refine_view.h's batch_prob and the two weight slices (the per-record output is the caller's)
+template <class A>
+__device__ __forceinline__ const double *weighted_prob(const A &a, int64_t b, WProb &wp)
 {
-    const cvx::ProblemView pv = cvx::make_view(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem);
-    wp.pb.n_p = a.n_p; wp.pb.n_l = a.n_l;
-    wp.pb.p2 = pv.p2; wp.pb.p3 = pv.p3; wp.pb.l2 = pv.l2; wp.pb.l3 = pv.l3;
-    wp.pb.mp = a.mp ? a.mp + b * a.n_p : nullptr;
-    wp.pb.ml = a.ml ? a.ml + b * a.n_l : nullptr;
+    const double *K = cvxr::batch_prob(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem, a.mp, a.ml, wp.pb);
     wp.wp = a.wp ? a.wp + b * a.n_p : nullptr;
     wp.wl = a.wl ? a.wl + b * a.n_l : nullptr;
+    return K;
+}
+
+// problem b of this library's batch form: rho'(s_k) of its records goes to rw_p, the points' then the lines'
+__device__ __forceinline__ const double *batch_prob(const BatchArgs &a, int64_t b, WProb &wp)
+{
+    const double *K = weighted_prob(a, b, wp);
     wp.ow_p = a.out.rw_p ? a.out.rw_p + b * ((int64_t)a.n_p + a.n_l) : nullptr;
     wp.ow_l = wp.ow_p ? wp.ow_p + a.n_p : nullptr;
-    return pv.K;
+    return K;
 }
 
 template <int RPL>
@@ -199,25 +205,14 @@ struct SceneArgs {
     Outputs out;
 };
 
-// the workgroup's scene (refine_kernel.h's scene_lanes with the weights): both slices clamped, K / R / t / scale_px staged in LDS
-__device__ __forceinline__ void scene_lanes(const SceneArgs &a, int64_t f, const double *R, const double *t, double *red, double *pose, WBlockLanes &ln)
+// the workgroup's scene with the weights: the poses R, t ([n_scenes][9] / [n_scenes][3]) staged in LDS with K and, behind them, the scale
+// of the loss (a.scale_px, or a scale of the scene's own: refine_robust_auto_kernel.h)
+__device__ __forceinline__ void scene_lanes(const SceneArgs &a, int64_t f, const double *R, const double *t, double scale, double *red, double *pose, WBlockLanes &ln)
 {
-    if (threadIdx.x < 9) pose[threadIdx.x] = a.K[(a.K_per_scene ? f * 9 : 0) + threadIdx.x];
-    else if (threadIdx.x < 18) pose[threadIdx.x] = R[9 * f + threadIdx.x - 9];
-    else if (threadIdx.x < 21) pose[threadIdx.x] = t[3 * f + threadIdx.x - 18];
-    else if (threadIdx.x == 21) pose[21] = a.scale_px; // (read back from LDS the loss is per-lane values too)
-    __syncthreads();
-    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts);
-    cvxn::Slice sl{0, 0};
-    if (a.off_l) sl = cvxn::scene_slice(a.off_l, f, a.n_lines);
+    cvxr::stage_pose(a.K, a.K_per_scene, R, t, f, pose, [&] { if (threadIdx.x == POSE_N) pose[POSE_N] = scale; }); // (read back from LDS the loss is per-lane values too)
+    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts), sl = cvxr::line_slice(a.off_l, f, a.n_lines);
     ln.b.red = red;
-    Prob &pb = ln.wp.pb;
-    pb.n_p = sp.n;
-    pb.n_l = sl.n > 0x7fffffff - sp.n ? 0x7fffffff - sp.n : sl.n;
-    pb.p2 = a.p2 + sp.beg * 2; pb.p3 = a.p3 + sp.beg * 3; // (never followed where the slice is empty)
-    pb.l2 = a.l2 + sl.beg * 4; pb.l3 = a.l3 + sl.beg * 6;
-    pb.mp = a.mp ? a.mp + sp.beg : nullptr;
-    pb.ml = a.ml ? a.ml + sl.beg : nullptr;
+    cvxr::scene_prob(sp, sl, a.p2, a.p3, a.l2, a.l3, a.mp, a.ml, ln.wp.pb);
     ln.wp.wp = in_vgpr(a.wp ? a.wp + sp.beg : nullptr); // (the scalar registers are full: see lane_outputs)
     ln.wp.wl = in_vgpr(a.wl ? a.wl + sl.beg : nullptr);
     ln.wp.ow_p = a.out.rw_p ? a.out.rw_p + sp.beg : nullptr;
@@ -227,17 +222,17 @@ __device__ __forceinline__ void scene_lanes(const SceneArgs &a, int64_t f, const
 __global__ void __launch_bounds__(TPB) refine_robust_scenes_kernel(SceneArgs a)
 {
     __shared__ double red[(WAVES + 1) * ACC_N];
-    __shared__ double pose[22];
+    __shared__ double pose[POSE_N + 1];
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return; // (workgroup-uniform)
     WBlockLanes ln;
-    scene_lanes(a, f, a.R, a.t, red, pose, ln);
+    scene_lanes(a, f, a.R, a.t, a.scale_px, red, pose, ln);
     const bool admit = !a.status || cvxr::admitted(a.status[f * a.status_stride], a.admit);
     const LaneOutputs lo = lane_outputs<6>(a.out, f);
     Result res;
     double c0;
     const double *ps = pose;
-    robust_problem(ln, ps, ps + 9, ps + 18, admit, a.opts, make_loss(a.loss_kind, ps[21]), res, c0);
+    robust_problem(ln, ps, ps + 9, ps + 18, admit, a.opts, make_loss(a.loss_kind, ps[POSE_N]), res, c0);
     if (threadIdx.x == 0) write_result<true>(lo, res, c0, ps + 9, ps + 18);
 }
 
@@ -245,13 +240,13 @@ __global__ void __launch_bounds__(TPB) refine_robust_scenes_kernel(SceneArgs a)
 __global__ void __launch_bounds__(TPB) robust_w_scenes_kernel(SceneArgs a)
 {
     __shared__ double red[(WAVES + 1) * ACC_N];
-    __shared__ double pose[22];
+    __shared__ double pose[POSE_N + 1];
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return;
     WBlockLanes ln;
-    scene_lanes(a, f, a.out.R, a.out.t, red, pose, ln);
+    scene_lanes(a, f, a.out.R, a.out.t, a.scale_px, red, pose, ln);
     const double *ps = pose;
-    const int n = robust_weights_problem(ln, ln.wp, ps, ps + 9, ps + 18, a.out.status[f], make_loss(a.loss_kind, ps[21]));
+    const int n = robust_weights_problem(ln, ln.wp, ps, ps + 9, ps + 18, a.out.status[f], make_loss(a.loss_kind, ps[POSE_N]));
     if (threadIdx.x == 0) a.out.n_inlier[f] = n;
 }
 

@@ -8,17 +8,20 @@
 //       LDS.  An empty group of the last wavefront shadows the last problem and writes nothing.
 //   refine_robust_vjp_scenes_kernel       packed scenes: one workgroup of 256 per scene; K, R, t, the upstream gradient and scale_px
 //       staged in LDS.
-// Both clamp what they index.  (refine_robust_kernel.h's three kernels that are not templates ride along into this library's code
-// object; nothing here launches them.)
+// Both clamp what they index; the views, the scenes' gradient slices and the staging are refine_view.h's, the weights' slices
+// refine_robust_kernel.h's weighted_prob.  (refine_robust_kernel.h's three kernels that are not templates ride along into this library's
+// code object; nothing here launches them.)
 #pragma once
-#include "ransac_common.h"
 #include "refine_lanes.h"
 #include "refine_robust_kernel.h"
 #include "refine_robust_vjp_core.h"
+#include "refine_view.h"
 
 namespace cvxrbg {
 
+using cvxr::POSE_N;
 using cvxr::TPB;
+using cvxr::UPSTREAM_N;
 using cvxr::WAVES;
 using cvxrb::in_vgpr;
 
@@ -43,14 +46,8 @@ __global__ void __launch_bounds__(TPB) refine_robust_vjp_group_kernel(VjpBatchAr
     const int64_t b = mine ? gi : a.batch - 1; // an empty group of the last wavefront shadows the last problem and writes nothing
     cvxrb::WGroupLanes<RPL> ln;
     ln.g.lane = threadIdx.x & 15;
-    const cvx::ProblemView pv = cvx::make_view(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem);
     WProb &wp = ln.wp;
-    wp.pb.n_p = a.n_p; wp.pb.n_l = a.n_l;
-    wp.pb.p2 = pv.p2; wp.pb.p3 = pv.p3; wp.pb.l2 = pv.l2; wp.pb.l3 = pv.l3;
-    wp.pb.mp = a.mp ? a.mp + b * a.n_p : nullptr;
-    wp.pb.ml = a.ml ? a.ml + b * a.n_l : nullptr;
-    wp.wp = a.wp ? a.wp + b * a.n_p : nullptr;
-    wp.wl = a.wl ? a.wl + b * a.n_l : nullptr;
+    const double *K = cvxrb::weighted_prob(a, b, wp);
     wp.ow_p = a.g_wp ? a.g_wp + b * a.n_p : nullptr; // (the weights' gradients: refine_robust_vjp_core.h)
     wp.ow_l = a.g_wl ? a.g_wl + b * a.n_l : nullptr;
     ln.load();
@@ -61,7 +58,7 @@ __global__ void __launch_bounds__(TPB) refine_robust_vjp_group_kernel(VjpBatchAr
     g.p3 = a.g_p3 ? a.g_p3 + b * a.n_p * 3 : nullptr;
     g.l2 = a.g_l2 ? a.g_l2 + b * a.n_l * 4 : nullptr;
     g.l3 = a.g_l3 ? a.g_l3 + b * a.n_l * 6 : nullptr;
-    const int st = robust_vjp_problem(ln, wp, pv.K, a.R + 9 * b, a.t + 3 * b, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, admit, mine, a.loss, g, writer && a.info ? a.info + 2 * b : nullptr);
+    const int st = robust_vjp_problem(ln, wp, K, a.R + 9 * b, a.t + 3 * b, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, admit, mine, a.loss, g, writer && a.info ? a.info + 2 * b : nullptr);
     if (writer) a.vstatus[b] = st;
 }
 
@@ -83,28 +80,19 @@ struct VjpSceneArgs {
 __global__ void __launch_bounds__(TPB) refine_robust_vjp_scenes_kernel(VjpSceneArgs a)
 {
     __shared__ double red[(WAVES + 1) * ACC_N];
-    __shared__ double pose[34]; // K, R, t, the upstream gradients G_R, g_t, scale_px: read from LDS they are per-lane values (refine_kernel.h)
+    constexpr int SCALE_AT = POSE_N + UPSTREAM_N;
+    __shared__ double pose[SCALE_AT + 1]; // K, R, t, the upstream gradients G_R, g_t (refine_view.h), scale_px
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return; // (workgroup-uniform)
-    if (threadIdx.x < 9) pose[threadIdx.x] = a.K[(a.K_per_scene ? f * 9 : 0) + threadIdx.x];
-    else if (threadIdx.x < 18) pose[threadIdx.x] = a.R[9 * f + threadIdx.x - 9];
-    else if (threadIdx.x < 21) pose[threadIdx.x] = a.t[3 * f + threadIdx.x - 18];
-    else if (threadIdx.x < 30) pose[threadIdx.x] = a.gR ? a.gR[9 * f + threadIdx.x - 21] : 0.0;
-    else if (threadIdx.x < 33) pose[threadIdx.x] = a.gt ? a.gt[3 * f + threadIdx.x - 30] : 0.0;
-    else if (threadIdx.x == 33) pose[33] = a.scale_px;
-    __syncthreads();
-    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts);
-    cvxn::Slice sl{0, 0};
-    if (a.off_l) sl = cvxn::scene_slice(a.off_l, f, a.n_lines);
+    const double *gR = a.gR, *gt = a.gt, scale_px = a.scale_px; // (captured as values: refine_vjp_kernel.h)
+    cvxr::stage_pose(a.K, a.K_per_scene, a.R, a.t, f, pose, [&] {
+        cvxr::stage_upstream(gR, gt, f, pose, [&] { if (threadIdx.x == SCALE_AT) pose[SCALE_AT] = scale_px; });
+    });
+    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts), sl = cvxr::line_slice(a.off_l, f, a.n_lines);
     cvxrb::WBlockLanes ln;
     ln.b.red = red;
     WProb &wp = ln.wp;
-    wp.pb.n_p = sp.n;
-    wp.pb.n_l = sl.n > 0x7fffffff - sp.n ? 0x7fffffff - sp.n : sl.n;
-    wp.pb.p2 = a.p2 + sp.beg * 2; wp.pb.p3 = a.p3 + sp.beg * 3; // (never followed where the slice is empty)
-    wp.pb.l2 = a.l2 + sl.beg * 4; wp.pb.l3 = a.l3 + sl.beg * 6;
-    wp.pb.mp = a.mp ? a.mp + sp.beg : nullptr;
-    wp.pb.ml = a.ml ? a.ml + sl.beg : nullptr;
+    cvxr::scene_prob(sp, sl, a.p2, a.p3, a.l2, a.l3, a.mp, a.ml, wp.pb);
     // (this kernel's scalar registers are full where its vector ones are not: the six pointers that the weights add live in vector
     // registers -- refine_robust_kernel.h's in_vgpr)
     wp.wp = in_vgpr(a.wp ? a.wp + sp.beg : nullptr);
@@ -113,12 +101,9 @@ __global__ void __launch_bounds__(TPB) refine_robust_vjp_scenes_kernel(VjpSceneA
     wp.ow_l = in_vgpr(a.g_wl ? a.g_wl + sl.beg : nullptr);
     const bool admit = !a.status || cvxr::admitted(a.status[f * a.status_stride], a.admit);
     Grads g;
-    g.p2 = a.g_p2 ? a.g_p2 + sp.beg * 2 : nullptr;
-    g.p3 = a.g_p3 ? a.g_p3 + sp.beg * 3 : nullptr;
-    g.l2 = a.g_l2 ? a.g_l2 + sl.beg * 4 : nullptr;
-    g.l3 = a.g_l3 ? a.g_l3 + sl.beg * 6 : nullptr;
+    cvxr::scene_grads(sp, sl, a.g_p2, a.g_p3, a.g_l2, a.g_l3, g);
     const double *ps = pose;
-    const int st = robust_vjp_problem(ln, wp, ps, ps + 9, ps + 18, ps + 21, ps + 30, admit, true, cvxrb::make_loss(a.loss_kind, ps[33]), g,
+    const int st = robust_vjp_problem(ln, wp, ps, ps + 9, ps + 18, ps + POSE_N, ps + POSE_N + 9, admit, true, cvxrb::make_loss(a.loss_kind, ps[SCALE_AT]), g,
                                       threadIdx.x == 0 && a.info ? a.info + 2 * f : nullptr);
     if (threadIdx.x == 0) a.vstatus[f] = st;
 }

@@ -7,15 +7,18 @@
 //       exchanges of width 16.  An empty group of the last wavefront shadows the last problem and writes nothing.  No LDS.
 //   refine_vjp_scenes_kernel       packed scenes: one workgroup of 256 per scene, K / R / t and the upstream gradient staged in LDS, the
 //       sums through BlockLanes' butterfly -> LDS -> fixed-order add; each thread then writes the gradients of the records it owns.
-// Both clamp what they index, as the kernels of refine_kernel.h do.
+// Both clamp what they index, as the kernels of refine_kernel.h do; the views, the scenes' gradient slices and the staging are
+// refine_view.h's (a batch problem's gradient slices stay here: as a function they changed the registers of all four group kernels).
 #pragma once
-#include "ransac_common.h"
 #include "refine_lanes.h"
+#include "refine_view.h"
 #include "refine_vjp_core.h"
 
 namespace cvxrg {
 
+using cvxr::POSE_N;
 using cvxr::TPB;
+using cvxr::UPSTREAM_N;
 using cvxr::WAVES;
 
 struct VjpBatchArgs {
@@ -38,11 +41,7 @@ __global__ void __launch_bounds__(TPB) refine_vjp_group_kernel(VjpBatchArgs a)
     const int64_t b = mine ? gi : a.batch - 1; // an empty group of the last wavefront shadows the last problem and writes nothing
     cvxr::GroupLanes<RPL> ln;
     ln.lane = threadIdx.x & 15;
-    const cvx::ProblemView pv = cvx::make_view(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem);
-    ln.pb.n_p = a.n_p; ln.pb.n_l = a.n_l;
-    ln.pb.p2 = pv.p2; ln.pb.p3 = pv.p3; ln.pb.l2 = pv.l2; ln.pb.l3 = pv.l3;
-    ln.pb.mp = a.mp ? a.mp + b * a.n_p : nullptr;
-    ln.pb.ml = a.ml ? a.ml + b * a.n_l : nullptr;
+    const double *K = cvxr::batch_prob(b, a.n_p, a.p2, a.p3, a.n_l, a.l2, a.l3, a.K, a.K_per_problem, a.mp, a.ml, ln.pb);
     ln.load();
     const bool admit = mine && (!a.status || cvxr::admitted(a.status[b * a.status_stride], a.admit));
     const bool writer = mine && ln.lane == 0;
@@ -51,7 +50,7 @@ __global__ void __launch_bounds__(TPB) refine_vjp_group_kernel(VjpBatchArgs a)
     g.p3 = a.g_p3 ? a.g_p3 + b * a.n_p * 3 : nullptr;
     g.l2 = a.g_l2 ? a.g_l2 + b * a.n_l * 4 : nullptr;
     g.l3 = a.g_l3 ? a.g_l3 + b * a.n_l * 6 : nullptr;
-    const int st = vjp_problem(ln, ln.lane, 16, pv.K, a.R + 9 * b, a.t + 3 * b, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, admit, mine,
+    const int st = vjp_problem(ln, ln.lane, 16, K, a.R + 9 * b, a.t + 3 * b, a.gR ? a.gR + 9 * b : nullptr, a.gt ? a.gt + 3 * b : nullptr, admit, mine,
                                g, writer && a.info ? a.info + 2 * b : nullptr);
     if (writer) a.vstatus[b] = st;
 }
@@ -72,34 +71,20 @@ struct VjpSceneArgs {
 __global__ void __launch_bounds__(TPB) refine_vjp_scenes_kernel(VjpSceneArgs a)
 {
     __shared__ double red[(WAVES + 1) * ACC_N];
-    __shared__ double pose[33]; // K, R, t, then the upstream gradients G_R, g_t: read from LDS they are per-lane values (refine_kernel.h)
+    __shared__ double pose[POSE_N + UPSTREAM_N]; // K, R, t, then the upstream gradients G_R, g_t (refine_view.h)
     const int64_t f = blockIdx.x;
     if (f >= a.n_scenes) return; // (workgroup-uniform)
-    if (threadIdx.x < 9) pose[threadIdx.x] = a.K[(a.K_per_scene ? f * 9 : 0) + threadIdx.x];
-    else if (threadIdx.x < 18) pose[threadIdx.x] = a.R[9 * f + threadIdx.x - 9];
-    else if (threadIdx.x < 21) pose[threadIdx.x] = a.t[3 * f + threadIdx.x - 18];
-    else if (threadIdx.x < 30) pose[threadIdx.x] = a.gR ? a.gR[9 * f + threadIdx.x - 21] : 0.0;
-    else if (threadIdx.x < 33) pose[threadIdx.x] = a.gt ? a.gt[3 * f + threadIdx.x - 30] : 0.0;
-    __syncthreads();
-    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts);
-    cvxn::Slice sl{0, 0};
-    if (a.off_l) sl = cvxn::scene_slice(a.off_l, f, a.n_lines);
+    const double *gR = a.gR, *gt = a.gt; // (captured as values: nothing here takes the address of the argument block -- refine_view.h)
+    cvxr::stage_pose(a.K, a.K_per_scene, a.R, a.t, f, pose, [&] { cvxr::stage_upstream(gR, gt, f, pose, [] {}); });
+    const cvxn::Slice sp = cvxn::scene_slice(a.off_p, f, a.n_pts), sl = cvxr::line_slice(a.off_l, f, a.n_lines);
     cvxr::BlockLanes ln;
     ln.red = red;
-    ln.pb.n_p = sp.n;
-    ln.pb.n_l = sl.n > 0x7fffffff - sp.n ? 0x7fffffff - sp.n : sl.n;
-    ln.pb.p2 = a.p2 + sp.beg * 2; ln.pb.p3 = a.p3 + sp.beg * 3; // (never followed where the slice is empty)
-    ln.pb.l2 = a.l2 + sl.beg * 4; ln.pb.l3 = a.l3 + sl.beg * 6;
-    ln.pb.mp = a.mp ? a.mp + sp.beg : nullptr;
-    ln.pb.ml = a.ml ? a.ml + sl.beg : nullptr;
+    cvxr::scene_prob(sp, sl, a.p2, a.p3, a.l2, a.l3, a.mp, a.ml, ln.pb);
     const bool admit = !a.status || cvxr::admitted(a.status[f * a.status_stride], a.admit);
     Grads g;
-    g.p2 = a.g_p2 ? a.g_p2 + sp.beg * 2 : nullptr;
-    g.p3 = a.g_p3 ? a.g_p3 + sp.beg * 3 : nullptr;
-    g.l2 = a.g_l2 ? a.g_l2 + sl.beg * 4 : nullptr;
-    g.l3 = a.g_l3 ? a.g_l3 + sl.beg * 6 : nullptr;
+    cvxr::scene_grads(sp, sl, a.g_p2, a.g_p3, a.g_l2, a.g_l3, g);
     const double *ps = pose;
-    const int st = vjp_problem(ln, (int)threadIdx.x, TPB, ps, ps + 9, ps + 18, ps + 21, ps + 30, admit, true, g,
+    const int st = vjp_problem(ln, (int)threadIdx.x, TPB, ps, ps + 9, ps + 18, ps + POSE_N, ps + POSE_N + 9, admit, true, g,
                                threadIdx.x == 0 && a.info ? a.info + 2 * f : nullptr);
     if (threadIdx.x == 0) a.vstatus[f] = st;
 }
