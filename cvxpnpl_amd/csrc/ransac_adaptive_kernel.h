@@ -20,7 +20,7 @@ namespace cvxna {
 
 using cvxn::SCENE_BLOCK;
 using cvxn::SCENE_WAVES;
-constexpr int ACTIVE_TILE = 512; // correspondences per LDS tile of the scoring kernel (20 KB), as cvxn::SCENE_TILE
+using cvxn::POINT_TILE;
 
 // ---- start of a call: every scene active, nothing drawn.  One lane per scene.
 struct InitArgs {
@@ -42,7 +42,8 @@ __global__ void __launch_bounds__(SCENE_BLOCK) adaptive_init_kernel(InitArgs a)
     a.hyp_used[f] = 0;
 }
 
-// ---- sampling: cvxn::sample_scenes_kernel with the scene indirection.  Grid (ceil(n_round / 256), active scenes of the slab).
+// ---- sampling: the scene indirection, then cvxn::hypothesis_K and cvxn::uniform_hypothesis with the counter hyp0 + h.
+// Grid (ceil(n_round / 256), active scenes of the slab).
 struct SampleActiveArgs {
     int64_t act0, n_active, n_scenes, n_total;
     int32_t hyp0, n_round;
@@ -64,32 +65,12 @@ __global__ void __launch_bounds__(SCENE_BLOCK) sample_active_kernel(SampleActive
     if (f < 0 || f >= a.n_scenes) return;
     const cvxn::Slice sl = cvxn::scene_slice(a.off, f, a.n_total);
     const int64_t g = ai * a.n_round + h;
-    if (a.Kh) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a.Kh[g * 9 + i] = a.K[f * 9 + i];
-    }
-    if (sl.n < 4) { // no draw is possible: the solve reports a non-finite pose
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (a.idx) a.idx[g * 4 + j] = -1;
-            a.p2[(g * 4 + j) * 2] = NAN; a.p2[(g * 4 + j) * 2 + 1] = NAN;
-            a.p3[(g * 4 + j) * 3] = NAN; a.p3[(g * 4 + j) * 3 + 1] = NAN; a.p3[(g * 4 + j) * 3 + 2] = NAN;
-        }
-        return;
-    }
-    int pick[4];
-    cvxn::draw_minimal_set(sl.n, a.seed[f], (uint32_t)(a.hyp0 + h), pick);
-    const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = pick[j]; // 0 .. M_f - 1 by construction
-        if (a.idx) a.idx[g * 4 + j] = c;
-        a.p2[(g * 4 + j) * 2] = s2[c * 2]; a.p2[(g * 4 + j) * 2 + 1] = s2[c * 2 + 1];
-        a.p3[(g * 4 + j) * 3] = s3[c * 3]; a.p3[(g * 4 + j) * 3 + 1] = s3[c * 3 + 1]; a.p3[(g * 4 + j) * 3 + 2] = s3[c * 3 + 2];
-    }
+    cvxn::hypothesis_K(a.K, f, a.Kh, g);
+    cvxn::uniform_hypothesis(sl, a.seed[f], a.hyp0 + h, a.s2, a.s3, g, a.idx, a.p2, a.p3);
 }
 
-// ---- scoring: cvxn::score_scenes_kernel with the scene indirection; the scene goes through LDS a tile at a time.  count [n_active * n_round].
+// ---- scoring: the scene indirection, then cvxn::hypothesis_usable and cvxn::score_points (the scene through LDS a tile at a time).
+// count [n_active * n_round].
 struct ScoreActiveArgs {
     int64_t act0, n_active, n_scenes, n_total;
     int32_t n_round;
@@ -106,7 +87,7 @@ struct ScoreActiveArgs {
 };
 __global__ void __launch_bounds__(SCENE_BLOCK) score_active_kernel(ScoreActiveArgs a)
 {
-    __shared__ double scene[ACTIVE_TILE * 5];
+    __shared__ double scene[POINT_TILE * 5];
     const int64_t ai = a.act0 + blockIdx.y;
     if (ai >= a.n_active) return; // (block-uniform)
     const int64_t f = a.active[ai];
@@ -117,34 +98,15 @@ __global__ void __launch_bounds__(SCENE_BLOCK) score_active_kernel(ScoreActiveAr
     const cvxn::Slice sl = cvxn::scene_slice(a.off, f, a.n_total);
     cvxn::Camera cam;
     cvxn::camera_load(a.R + g * 9, a.t + g * 3, a.K + (a.K_per_scene ? f * 9 : 0), cam);
-    bool usable = live;
-    if (live && a.status) {
-        const int32_t s = a.status[g];
-        usable = s >= 0 && s < 32 && ((a.usable_mask >> s) & 1u);
-    }
+    const bool usable = cvxn::hypothesis_usable(live, a.status, g, a.usable_mask);
     const double th2 = a.thresh * a.thresh;
     const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
-    int cnt = 0;
-    for (int base = 0; base < sl.n; base += ACTIVE_TILE) {
-        const int n = sl.n - base < ACTIVE_TILE ? sl.n - base : ACTIVE_TILE;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += SCENE_BLOCK) {
-            const int64_t m = base + i;
-            scene[i * 5 + 0] = s3[m * 3 + 0];
-            scene[i * 5 + 1] = s3[m * 3 + 1];
-            scene[i * 5 + 2] = s3[m * 3 + 2];
-            scene[i * 5 + 3] = s2[m * 2 + 0];
-            scene[i * 5 + 4] = s2[m * 2 + 1];
-        }
-        __syncthreads();
-        for (int i = 0; i < n; ++i)
-            cnt += usable && cvxn::is_inlier(cam, scene[i * 5], scene[i * 5 + 1], scene[i * 5 + 2], scene[i * 5 + 3], scene[i * 5 + 4], th2) ? 1 : 0;
-    }
+    const int cnt = cvxn::score_points<int>(scene, sl.n, s2, s3, cam, usable, th2);
     if (live) a.count[g] = cnt;
 }
 
-// ---- the round's update: ONE workgroup per active scene.  The arg-max of the round's counts (lowest index on a tie, as
-// cvxn::select_scenes_kernel), merged into the scene's running best by a STRICTLY greater count, so that an earlier hypothesis keeps a
+// ---- the round's update: ONE workgroup per active scene.  The arg-max of the round's counts (cvxn::block_argmax: lowest index on a
+// tie), merged into the scene's running best by a STRICTLY greater count, so that an earlier hypothesis keeps a
 // tie over the rounds as it does within one.  best[f] is the count the scoring kernel gave the running winner (head[f][1] is the size of
 // the mask it was scored again for: the same for a usable winner, and not 0 for an unusable one).  On replacement pose, head[f][0..2]
 // and the scene's slice of the mask change together; certified hypotheses accumulate in head[f][3]; then the stopping rule.
@@ -178,27 +140,9 @@ __global__ void __launch_bounds__(SCENE_BLOCK) round_update_kernel(RoundUpdateAr
     const int64_t f = a.active[ai];
     if (f < 0 || f >= a.n_scenes) return; // (block-uniform) skipped, not clamped
     const int64_t g0 = ai * a.n_round;
-    // (count, index) packed so that a plain max picks the highest count and, among equals, the LOWEST index
-    long long best = -1;
-    int cert = 0;
-    for (int h = threadIdx.x; h < a.n_round; h += SCENE_BLOCK) {
-        const long long key = ((long long)a.count[g0 + h] << 32) | (long long)(0x7fffffff - h);
-        best = key > best ? key : best;
-        cert += a.status[g0 + h] == 0 ? 1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long ob = __shfl_down(best, o);
-        best = ob > best ? ob : best;
-        cert += __shfl_down(cert, o);
-    }
-    if ((threadIdx.x & 63) == 0) { best_w[threadIdx.x >> 6] = best; cert_w[threadIdx.x >> 6] = cert; }
-    __syncthreads();
-    best = best_w[0]; cert = cert_w[0];
-#pragma unroll
-    for (int wv = 1; wv < SCENE_WAVES; ++wv) { best = best_w[wv] > best ? best_w[wv] : best; cert += cert_w[wv]; }
-    int hb = (int)(0x7fffffffLL - (best & 0xffffffffLL));
-    hb = hb < 0 || hb >= a.n_round ? 0 : hb; // (a corrupt count must not index outside the round's hypotheses)
-    const int cnt_round = (int)(best >> 32);
+    const cvxn::Winner w = cvxn::block_argmax<int>(a.count, a.status, g0, a.n_round, best_w, cert_w);
+    const int hb = w.h, cert = w.cert;
+    const int cnt_round = w.count;
     const int cnt_prev = a.best[f];
     const bool replace = cnt_round > cnt_prev; // (workgroup-uniform)
     const cvxn::Slice sl = cvxn::scene_slice(a.off, f, a.n_total);
@@ -207,8 +151,7 @@ __global__ void __launch_bounds__(SCENE_BLOCK) round_update_kernel(RoundUpdateAr
         cvxn::Camera cam;
         cvxn::camera_load(a.R + gb * 9, a.t + gb * 3, a.K + (a.K_per_scene ? f * 9 : 0), cam);
         const int n_inl = cvxn::block_inliers(cam, sl.n, a.s2 + sl.beg * 2, a.s3 + sl.beg * 3, a.thresh * a.thresh, a.mask + sl.beg, red);
-        if (threadIdx.x < 9) a.out_R[f * 9 + threadIdx.x] = a.R[gb * 9 + threadIdx.x];
-        if (threadIdx.x < 3) a.out_t[f * 3 + threadIdx.x] = a.t[gb * 3 + threadIdx.x];
+        cvxn::take_pose(a.R, a.t, gb, a.out_R, a.out_t, f);
         if (threadIdx.x == 0) { a.head[f * 4] = a.status[gb]; a.head[f * 4 + 1] = n_inl; a.head[f * 4 + 2] = a.hyp0 + hb; a.best[f] = cnt_round; }
     }
     if (threadIdx.x == 0) {

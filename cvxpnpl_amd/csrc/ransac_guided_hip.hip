@@ -35,16 +35,6 @@ const char *check_draw(const int64_t *off, int64_t n_total, const double *s2, co
     return nullptr;
 }
 
-// the clamped slice of a scene on the host: cvxn::scene_slice
-void host_slice(const int64_t *off, int64_t f, int64_t n_total, int64_t &beg, int64_t &n)
-{
-    int64_t e = off[f + 1], b = off[f];
-    e = e < 0 ? 0 : (e > n_total ? n_total : e);
-    b = b < 0 ? 0 : (b > e ? e : b);
-    n = e - b > 0x7fffffffLL ? 0x7fffffffLL : e - b;
-    beg = b;
-}
-
 } // namespace
 
 extern "C" const char *cvxpnpl_ransac_guided_last_error(void) { return err_buf(); }
@@ -67,8 +57,8 @@ extern "C" int cvxpnpl_ransac_guided_rank_host(int64_t n_scenes, const int64_t *
     if (!order) return bad_args(who, "order is null");
     cvxh::for_chunks(n_scenes, n_threads, [&](int64_t lo, int64_t hi) {
         for (int64_t f = lo; f < hi; ++f) {
-            int64_t beg, n;
-            host_slice(offsets, f, n_total, beg, n);
+            const cvxn::Slice sl = cvxn::scene_slice(offsets, f, n_total);
+            const int64_t beg = sl.beg, n = sl.n;
             const double *q = quality + beg;
             for (int64_t m = 0; m < n; ++m) { // the kernel's lane m
                 const double key = cvxng::quality_key(q[m]);

@@ -2,12 +2,12 @@
 // DESIGN.md section 20).  A scene's correspondences carry a quality; rank_quality_kernel turns it into order [n_total] int32, per scene a
 // permutation of 0 .. M_f - 1, best first.  Hypothesis h of a scene then draws draw_minimal_set(n(h), seed_f, h) -- n(h) = cvxng::pool_size,
 // which depends on (h, M_f, pool_full) alone -- and takes order[beg_f + pick[j]] as its correspondences; from h = pool_full on the draw is
-// the uniform one of cvxn::sample_scenes_kernel, used directly.  The Philox counter stays the hypothesis index within the scene, so a
+// the uniform one of cvxn::uniform_hypothesis, used directly.  The Philox counter stays the hypothesis index within the scene, so a
 // scene's hypotheses are the same whether they come in one launch (sample_guided_kernel) or in rounds (sample_guided_active_kernel, the
 // layout of cvxna::sample_active_kernel).
 //
-// Slices are clamped to [0, n_total) as in ransac_kernel.h.  An order entry outside [0, M_f) never becomes an address: the hypothesis is
-// written as the NaN hypothesis of a short scene.  Every loop is bounded by M_f or a constant; nothing waits for another workgroup; no
+// Slices are clamped to [0, n_total) by cvxn::scene_slice.  An order entry outside [0, M_f) never becomes an address: the hypothesis is
+// written as the NaN hypothesis of a short scene (cvxn::write_point_set).  Every loop is bounded by M_f or a constant; nothing waits for another workgroup; no
 // atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -71,26 +71,11 @@ __device__ inline void guided_hypothesis(const cvxn::Slice sl, uint64_t seed, in
             }
         }
     }
-    if (!ok) { // no draw is possible, or the ranking is no ranking: the solve reports a non-finite pose
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (idx) idx[g * 4 + j] = -1;
-            p2[(g * 4 + j) * 2] = NAN; p2[(g * 4 + j) * 2 + 1] = NAN;
-            p3[(g * 4 + j) * 3] = NAN; p3[(g * 4 + j) * 3 + 1] = NAN; p3[(g * 4 + j) * 3 + 2] = NAN;
-        }
-        return;
-    }
-    const double *s2 = scene2 + sl.beg * 2, *s3 = scene3 + sl.beg * 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = pick[j];
-        if (idx) idx[g * 4 + j] = c;
-        p2[(g * 4 + j) * 2] = s2[c * 2]; p2[(g * 4 + j) * 2 + 1] = s2[c * 2 + 1];
-        p3[(g * 4 + j) * 3] = s3[c * 3]; p3[(g * 4 + j) * 3 + 1] = s3[c * 3 + 1]; p3[(g * 4 + j) * 3 + 2] = s3[c * 3 + 2];
-    }
+    // (!ok: no draw is possible, or the ranking is no ranking: the solve reports a non-finite pose)
+    cvxn::write_point_set(ok, pick, sl.beg, scene2, scene3, g, idx, p2, p3);
 }
 
-// ---- sampling, every scene: cvxn::sample_scenes_kernel with the pool and the ranking.  Grid (ceil(H / 256), scenes of the slab).
+// ---- sampling, every scene: the fixed layout, cvxn::hypothesis_K, then guided_hypothesis.  Grid (ceil(H / 256), scenes of the slab).
 struct SampleGuidedArgs {
     int64_t scene0, n_scenes, n_total;
     int32_t n_hyp, pool_full;
@@ -110,14 +95,11 @@ __global__ void __launch_bounds__(SCENE_BLOCK) sample_guided_kernel(SampleGuided
     if (f >= a.n_scenes || h >= a.n_hyp) return;
     const cvxn::Slice sl = cvxn::scene_slice(a.off, f, a.n_total);
     const int64_t g = f * a.n_hyp + h;
-    if (a.Kh) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a.Kh[g * 9 + i] = a.K[f * 9 + i];
-    }
+    cvxn::hypothesis_K(a.K, f, a.Kh, g);
     guided_hypothesis(sl, a.seed[f], h, a.pool_full, a.order, a.s2, a.s3, g, a.idx, a.p2, a.p3);
 }
 
-// ---- sampling, the active scenes of a round: cvxna::sample_active_kernel with the pool and the ranking.  Entry a is scene f = active[a],
+// ---- sampling, the active scenes of a round: the scene indirection of cvxna::sample_active_kernel, cvxn::hypothesis_K, then guided_hypothesis.  Entry a is scene f = active[a],
 // hypothesis h of the round is hypothesis hyp0 + h of the scene and problem a * n_round + h.  Grid (ceil(n_round / 256), entries of the slab).
 struct SampleGuidedActiveArgs {
     int64_t act0, n_active, n_scenes, n_total;
@@ -141,10 +123,7 @@ __global__ void __launch_bounds__(SCENE_BLOCK) sample_guided_active_kernel(Sampl
     if (f < 0 || f >= a.n_scenes) return; // skipped, not clamped
     const cvxn::Slice sl = cvxn::scene_slice(a.off, f, a.n_total);
     const int64_t g = ai * a.n_round + h;
-    if (a.Kh) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a.Kh[g * 9 + i] = a.K[f * 9 + i];
-    }
+    cvxn::hypothesis_K(a.K, f, a.Kh, g);
     guided_hypothesis(sl, a.seed[f], a.hyp0 + h, a.pool_full, a.order, a.s2, a.s3, g, a.idx, a.p2, a.p3); // hyp0 + h < cap: no wrap
 }
 

@@ -15,8 +15,8 @@
 
 namespace cvxn {
 
-// (SCENE_BLOCK, the lanes of every workgroup here, SCENE_WAVES and block_inliers: ransac_common.h)
-constexpr int SCENE_TILE = 512;   // correspondences per LDS tile of the scoring kernel (20 KB)
+// (SCENE_BLOCK, the lanes of every workgroup here, SCENE_WAVES, POINT_TILE and the steps the kernels call: ransac_common.h; those of the
+// consensus assembly: ransac_consensus.h)
 
 // ---- sampling: one lane per (scene, hypothesis), grid (ceil(H / 256), scenes).  The draw of cvxs::sample_sets_kernel for k = 4 over the
 // scene's own M_f, with the scene's own seed as the Philox key and the hypothesis index WITHIN the scene as the counter: scene f draws
@@ -39,33 +39,12 @@ __global__ void __launch_bounds__(SCENE_BLOCK) sample_scenes_kernel(SampleScenes
     if (f >= a.n_scenes || h >= a.n_hyp) return;
     const Slice sl = scene_slice(a.off, f, a.n_total);
     const int64_t g = f * a.n_hyp + h;
-    if (a.Kh) {
-#pragma unroll
-        for (int i = 0; i < 9; ++i) a.Kh[g * 9 + i] = a.K[f * 9 + i];
-    }
-    if (sl.n < 4) { // (refused by the Python entry point; here: no draw is possible, the solve reports a non-finite pose)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (a.idx) a.idx[g * 4 + j] = -1;
-            a.p2[(g * 4 + j) * 2] = NAN; a.p2[(g * 4 + j) * 2 + 1] = NAN;
-            a.p3[(g * 4 + j) * 3] = NAN; a.p3[(g * 4 + j) * 3 + 1] = NAN; a.p3[(g * 4 + j) * 3 + 2] = NAN;
-        }
-        return;
-    }
-    int pick[4];
-    draw_minimal_set(sl.n, a.seed[f], (uint32_t)h, pick);
-    const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        const int c = pick[j]; // 0 .. M_f - 1 by construction
-        if (a.idx) a.idx[g * 4 + j] = c;
-        a.p2[(g * 4 + j) * 2] = s2[c * 2]; a.p2[(g * 4 + j) * 2 + 1] = s2[c * 2 + 1];
-        a.p3[(g * 4 + j) * 3] = s3[c * 3]; a.p3[(g * 4 + j) * 3 + 1] = s3[c * 3 + 1]; a.p3[(g * 4 + j) * 3 + 2] = s3[c * 3 + 2];
-    }
+    hypothesis_K(a.K, f, a.Kh, g);
+    uniform_hypothesis(sl, a.seed[f], h, a.s2, a.s3, g, a.idx, a.p2, a.p3);
 }
 
 // ---- scoring: grid (ceil(H / 256), scenes), one lane per hypothesis of the workgroup's scene; the scene is staged through LDS a tile at
-// a time and broadcast to the lanes, as cvxs::score_kernel does.  count [n_scenes * n_hyp].
+// a time and broadcast to the lanes (score_points), a hypothesis outside usable_mask scoring nothing (hypothesis_usable).  count [n_scenes * n_hyp].
 struct ScoreScenesArgs {
     int64_t scene0, n_scenes, n_total;
     int32_t n_hyp;
@@ -81,7 +60,7 @@ struct ScoreScenesArgs {
 };
 __global__ void __launch_bounds__(SCENE_BLOCK) score_scenes_kernel(ScoreScenesArgs a)
 {
-    __shared__ double scene[SCENE_TILE * 5];
+    __shared__ double scene[POINT_TILE * 5];
     const int64_t f = a.scene0 + blockIdx.y;
     if (f >= a.n_scenes) return; // (block-uniform)
     const int32_t h = (int32_t)(blockIdx.x * SCENE_BLOCK + threadIdx.x);
@@ -90,35 +69,16 @@ __global__ void __launch_bounds__(SCENE_BLOCK) score_scenes_kernel(ScoreScenesAr
     const Slice sl = scene_slice(a.off, f, a.n_total);
     Camera cam;
     camera_load(a.R + g * 9, a.t + g * 3, a.K + (a.K_per_scene ? f * 9 : 0), cam);
-    bool usable = live;
-    if (live && a.status) {
-        const int32_t s = a.status[g];
-        usable = s >= 0 && s < 32 && ((a.usable_mask >> s) & 1u);
-    }
+    const bool usable = hypothesis_usable(live, a.status, g, a.usable_mask);
     const double th2 = a.thresh * a.thresh;
     const double *s2 = a.s2 + sl.beg * 2, *s3 = a.s3 + sl.beg * 3;
-    int cnt = 0;
-    for (int base = 0; base < sl.n; base += SCENE_TILE) {
-        const int n = sl.n - base < SCENE_TILE ? sl.n - base : SCENE_TILE;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += SCENE_BLOCK) {
-            const int64_t m = base + i;
-            scene[i * 5 + 0] = s3[m * 3 + 0];
-            scene[i * 5 + 1] = s3[m * 3 + 1];
-            scene[i * 5 + 2] = s3[m * 3 + 2];
-            scene[i * 5 + 3] = s2[m * 2 + 0];
-            scene[i * 5 + 4] = s2[m * 2 + 1];
-        }
-        __syncthreads();
-        for (int i = 0; i < n; ++i)
-            cnt += usable && is_inlier(cam, scene[i * 5], scene[i * 5 + 1], scene[i * 5 + 2], scene[i * 5 + 3], scene[i * 5 + 4], th2) ? 1 : 0;
-    }
+    const int cnt = score_points<int>(scene, sl.n, s2, s3, cam, usable, th2);
     if (live) a.count[g] = cnt;
 }
 
 // ---- selection: ONE workgroup per scene.  Arg-max of the scene's H counts with the LOWEST index winning a tie, the number of certified
 // hypotheses on the way, then the winner's pose and -- scored again by the workgroup's lanes -- its mask in the scene's slice of the
-// packed mask.  head[f] = { status of the pose, inliers, index of the winner within the scene, certified hypotheses }.
+// packed mask.  (The arg-max is a copy of cvxn::block_argmax: DESIGN.md section 13 says why.)  head[f] = { status of the pose, inliers, index of the winner within the scene, certified hypotheses }.
 struct SelectScenesArgs {
     int64_t n_scenes, n_total;
     int32_t n_hyp;

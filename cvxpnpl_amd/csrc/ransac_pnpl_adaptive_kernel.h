@@ -25,7 +25,7 @@ using cvxn::Camera;
 using cvxnl::BLOCK;
 using cvxnl::Scene;
 using cvxnl::SceneSet;
-using cvxnl::WAVES;
+using cvxn::SCENE_WAVES;
 
 // ---- sampling and minimal assembly of a round: cvxnl::sample_assemble_kernel with the scene indirection, the pool and the ranking.
 // Grid (ceil(n_round / 256), entries of the slab).  Hypothesis hs = hyp0 + h draws draw_minimal_set(pool_size(hs, M_f, pool_full),
@@ -58,7 +58,8 @@ __global__ void __launch_bounds__(BLOCK) sample_assemble_active_kernel(SampleArg
     cvxnl::minimal_hypothesis(sc, a.seed[f], hs, pool, ranked, ai * a.n_round + h64, a.idx, a.Q45, a.B27);
 }
 
-// ---- scoring of a round: cvxnl::score_kernel with the scene indirection and the compact layout.  count [n_active * n_round].
+// ---- scoring of a round: the scene indirection and the compact layout, then cvxn::hypothesis_usable and cvxnl::score_scene.
+// count [n_active * n_round].
 struct ScoreArgs {
     SceneSet s;
     int64_t act0, n_active;
@@ -83,17 +84,13 @@ __global__ void __launch_bounds__(BLOCK) score_pnpl_active_kernel(ScoreArgs a)
     const Scene sc = cvxnl::scene_of(a.s, f);
     Camera cam;
     cvxn::camera_load(a.R + g * 9, a.t + g * 3, sc.K, cam);
-    bool usable = live;
-    if (live && a.status) {
-        const int32_t s = a.status[g];
-        usable = s >= 0 && s < 32 && ((a.usable_mask >> s) & 1u);
-    }
+    const bool usable = cvxn::hypothesis_usable(live, a.status, g, a.usable_mask);
     const int cnt = cvxnl::score_scene(tile, sc, cam, usable, a.thresh);
     if (live) a.count[g] = cnt;
 }
 
 // ---- the round's update: ONE workgroup per active scene, cvxna::round_update_kernel with two masks.  The arg-max of the round's counts
-// (lowest index on a tie, as cvxnl::select_kernel), merged into the scene's running best by a STRICTLY greater count, so that an earlier
+// (cvxn::block_argmax: lowest index on a tie), merged into the scene's running best by a STRICTLY greater count, so that an earlier
 // hypothesis keeps a tie over the rounds as it does within one.  best[f] is the count the scoring kernel gave the running winner
 // (head[f][1] is the size of the masks it was scored again for).  On replacement pose, head[f][0..2] and the scene's slices of both masks
 // change together; certified hypotheses accumulate in head[f][3]; then the stopping rule on M_f = P_f + L_f.
@@ -116,35 +113,17 @@ struct UpdateArgs {
 };
 __global__ void __launch_bounds__(BLOCK) update_pnpl_active_kernel(UpdateArgs a)
 {
-    __shared__ int red[WAVES];
-    __shared__ long long best_w[WAVES];
-    __shared__ int cert_w[WAVES];
+    __shared__ int red[SCENE_WAVES];
+    __shared__ long long best_w[SCENE_WAVES];
+    __shared__ int cert_w[SCENE_WAVES];
     const int64_t ai = blockIdx.x;
     if (ai >= a.n_active) return;
     const int64_t f = a.active[ai];
     if (f < 0 || f >= a.s.n_scenes) return; // (block-uniform) skipped, not clamped
     const int64_t g0 = ai * a.n_round;
-    // (count, index) packed so that a plain max picks the highest count and, among equals, the LOWEST index
-    long long best = -1;
-    int cert = 0;
-    for (int h = threadIdx.x; h < a.n_round; h += BLOCK) {
-        const long long key = ((long long)a.count[g0 + h] << 32) | (long long)(0x7fffffff - h);
-        best = key > best ? key : best;
-        cert += a.status[g0 + h] == 0 ? 1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long ob = __shfl_down(best, o);
-        best = ob > best ? ob : best;
-        cert += __shfl_down(cert, o);
-    }
-    if ((threadIdx.x & 63) == 0) { best_w[threadIdx.x >> 6] = best; cert_w[threadIdx.x >> 6] = cert; }
-    __syncthreads();
-    best = best_w[0]; cert = cert_w[0];
-#pragma unroll
-    for (int wv = 1; wv < WAVES; ++wv) { best = best_w[wv] > best ? best_w[wv] : best; cert += cert_w[wv]; }
-    int hb = (int)(0x7fffffffLL - (best & 0xffffffffLL));
-    hb = hb < 0 || hb >= a.n_round ? 0 : hb; // (a corrupt count must not index outside the round's hypotheses)
-    const int cnt_round = (int)(best >> 32);
+    const cvxn::Winner w = cvxn::block_argmax<int>(a.count, a.status, g0, a.n_round, best_w, cert_w);
+    const int hb = w.h, cert = w.cert;
+    const int cnt_round = w.count;
     const int cnt_prev = a.best[f];
     const bool replace = cnt_round > cnt_prev; // (workgroup-uniform)
     const Scene sc = cvxnl::scene_of(a.s, f);
@@ -153,8 +132,7 @@ __global__ void __launch_bounds__(BLOCK) update_pnpl_active_kernel(UpdateArgs a)
         Camera cam;
         cvxn::camera_load(a.R + gb * 9, a.t + gb * 3, sc.K, cam);
         const int n_inl = cvxnl::block_inliers(cam, sc, a.thresh, a.mask_p + sc.beg_p, a.mask_l + sc.beg_l, red);
-        if (threadIdx.x < 9) a.out_R[f * 9 + threadIdx.x] = a.R[gb * 9 + threadIdx.x];
-        if (threadIdx.x < 3) a.out_t[f * 3 + threadIdx.x] = a.t[gb * 3 + threadIdx.x];
+        cvxn::take_pose(a.R, a.t, gb, a.out_R, a.out_t, f);
         if (threadIdx.x == 0) { a.head[f * 4] = a.status[gb]; a.head[f * 4 + 1] = n_inl; a.head[f * 4 + 2] = a.hyp0 + hb; a.best[f] = cnt_round; }
     }
     if (threadIdx.x == 0) {

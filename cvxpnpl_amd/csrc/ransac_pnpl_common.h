@@ -16,10 +16,10 @@ namespace cvxnl {
 using cvxn::Camera;
 using cvxn::Slice;
 
-constexpr int BLOCK = 256;       // lanes of the sampling / scoring / selection / refit workgroups
-constexpr int WAVES = BLOCK / 64;
-constexpr int POINT_TILE = 512;  // points per LDS tile of the scoring kernel: 5 doubles each (20 KB)
-constexpr int LINE_TILE = 256;   // lines per LDS tile: 9 doubles each (18 KB), in the same buffer
+using cvxn::POINT_TILE;
+using cvxn::SCENE_WAVES;
+constexpr int BLOCK = cvxn::SCENE_BLOCK; // (the name the entry files launch with)
+constexpr int LINE_TILE = 256;           // lines per LDS tile: 9 doubles each (18 KB), in the buffer of POINT_TILE points
 constexpr int TILE_DOUBLES = POINT_TILE * 5;
 static_assert(LINE_TILE * 9 <= TILE_DOUBLES && LINE_TILE <= BLOCK, "a line tile fits the buffer and is staged one line per lane");
 
@@ -84,7 +84,7 @@ __device__ inline bool is_line_inlier(const Camera &c, const double *ab /* u0 v0
 }
 
 // ---- one hypothesis, from the draw to the cost, by one lane: hypothesis h (index within the scene: the Philox counter) of scene sc,
-// written as problem g.  The draw is that of cvxn::sample_scenes_kernel (cvxn::draw_minimal_set: same key, same counter) over the first
+// written as problem g.  The draw is that of cvxn::uniform_hypothesis (cvxn::draw_minimal_set: same key, same counter) over the first
 // `pool` of the scene's M_f = P_f + L_f correspondences; index c < P_f is point c, otherwise line c - P_f.  ranked (optional): the
 // scene's ranking, the draw is then a set of ranks and the set is ranked[pick[j]]; an entry outside [0, M_f) never becomes an address,
 // the hypothesis is then written as that of a scene too short to draw from.  The lane assembles its set in place, in the order and about
@@ -176,28 +176,12 @@ __device__ inline void minimal_hypothesis(const Scene &sc, uint64_t seed, int32_
 }
 
 // ---- the inliers of one pose per LANE over one scene, by a workgroup of BLOCK lanes.  The scene's points go through LDS a tile at a
-// time and are broadcast to the lanes, as in cvxn::score_scenes_kernel; then its lines, a tile of end points plus the NORMALISED image
+// time and are broadcast to the lanes (cvxn::score_points); then its lines, a tile of end points plus the NORMALISED image
 // line, computed once per tile by the lane that stages the line.  Every lane of the workgroup calls it (barriers); a lane that is not
 // usable counts nothing.  Returns point inliers + line inliers of the lane's pose.
 __device__ inline int score_scene(double *tile /* LDS, TILE_DOUBLES */, const Scene &sc, const Camera &cam, bool usable, double thresh)
 {
-    const double th2 = thresh * thresh;
-    int cnt = 0;
-    for (int64_t base = 0; base < sc.P; base += POINT_TILE) {
-        const int n = sc.P - base < POINT_TILE ? (int)(sc.P - base) : POINT_TILE;
-        __syncthreads();
-        for (int i = threadIdx.x; i < n; i += BLOCK) {
-            const int64_t m = base + i;
-            tile[i * 5 + 0] = sc.p3[m * 3 + 0];
-            tile[i * 5 + 1] = sc.p3[m * 3 + 1];
-            tile[i * 5 + 2] = sc.p3[m * 3 + 2];
-            tile[i * 5 + 3] = sc.p2[m * 2 + 0];
-            tile[i * 5 + 4] = sc.p2[m * 2 + 1];
-        }
-        __syncthreads();
-        for (int i = 0; i < n; ++i)
-            cnt += usable && cvxn::is_inlier(cam, tile[i * 5], tile[i * 5 + 1], tile[i * 5 + 2], tile[i * 5 + 3], tile[i * 5 + 4], th2) ? 1 : 0;
-    }
+    int cnt = cvxn::score_points<int64_t>(tile, sc.P, sc.p2, sc.p3, cam, usable, thresh * thresh);
     for (int64_t base = 0; base < sc.L; base += LINE_TILE) {
         const int n = sc.L - base < LINE_TILE ? (int)(sc.L - base) : LINE_TILE;
         __syncthreads();
@@ -219,7 +203,7 @@ __device__ inline int score_scene(double *tile /* LDS, TILE_DOUBLES */, const Sc
 
 // inliers of ONE pose over one scene's points and lines, by the lanes of one workgroup: writes both masks (optional, together) and returns
 // points + lines to every lane
-__device__ inline int block_inliers(const Camera &cam, const Scene &sc, double thresh, uint8_t *mask_p, uint8_t *mask_l, int *red /* LDS, WAVES ints */)
+__device__ inline int block_inliers(const Camera &cam, const Scene &sc, double thresh, uint8_t *mask_p, uint8_t *mask_l, int *red /* LDS, SCENE_WAVES ints */)
 {
     const double th2 = thresh * thresh;
     int cnt = 0;
@@ -241,7 +225,7 @@ __device__ inline int block_inliers(const Camera &cam, const Scene &sc, double t
     __syncthreads();
     int tot = 0;
 #pragma unroll
-    for (int wv = 0; wv < WAVES; ++wv) tot += red[wv];
+    for (int wv = 0; wv < SCENE_WAVES; ++wv) tot += red[wv];
     return tot;
 }
 

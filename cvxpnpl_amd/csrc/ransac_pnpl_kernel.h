@@ -42,7 +42,7 @@ __global__ void __launch_bounds__(BLOCK) sample_assemble_kernel(SampleArgs a)
 }
 
 // ---- scoring: grid (ceil(H / 256), scenes), one lane per hypothesis of the workgroup's scene.  The scene's points go through LDS a tile
-// at a time and are broadcast to the lanes, as in cvxn::score_scenes_kernel; then its lines, a tile of end points plus the NORMALISED
+// at a time and are broadcast to the lanes (cvxn::score_points); then its lines, a tile of end points plus the NORMALISED
 // image line, computed once per tile by the lane that stages the line.  count [n_scenes * n_hyp] = point inliers + line inliers.
 struct ScoreArgs {
     SceneSet s;
@@ -65,17 +65,13 @@ __global__ void __launch_bounds__(BLOCK) score_kernel(ScoreArgs a)
     const Scene sc = scene_of(a.s, f);
     Camera cam;
     cvxn::camera_load(a.R + g * 9, a.t + g * 3, sc.K, cam);
-    bool usable = live;
-    if (live && a.status) {
-        const int32_t s = a.status[g];
-        usable = s >= 0 && s < 32 && ((a.usable_mask >> s) & 1u);
-    }
+    const bool usable = cvxn::hypothesis_usable(live, a.status, g, a.usable_mask);
     const int cnt = score_scene(tile, sc, cam, usable, a.thresh);
     if (live) a.count[g] = cnt;
 }
 
 // ---- selection: ONE workgroup per scene, cvxn::select_scenes_kernel with two masks.  Arg-max of the scene's H counts with the LOWEST
-// index winning a tie, the number of certified hypotheses on the way, then the winner's pose and -- scored again by the workgroup's
+// index winning a tie (cvxn::block_argmax), the number of certified hypotheses on the way, then the winner's pose and -- scored again by the workgroup's
 // lanes -- its masks.  head[f] = { status of the pose, inliers (points + lines), index of the winner within the scene, certified }.
 struct SelectArgs {
     SceneSet s;
@@ -90,39 +86,20 @@ struct SelectArgs {
 };
 __global__ void __launch_bounds__(BLOCK) select_kernel(SelectArgs a)
 {
-    __shared__ int red[WAVES];
-    __shared__ long long best_w[WAVES];
-    __shared__ int cert_w[WAVES];
+    __shared__ int red[SCENE_WAVES];
+    __shared__ long long best_w[SCENE_WAVES];
+    __shared__ int cert_w[SCENE_WAVES];
     const int64_t f = blockIdx.x;
     if (f >= a.s.n_scenes) return;
     const int64_t g0 = f * a.n_hyp;
-    // (count, index) packed so that a plain max picks the highest count and, among equals, the LOWEST index
-    long long best = -1;
-    int cert = 0;
-    for (int64_t h = threadIdx.x; h < a.n_hyp; h += BLOCK) {
-        const long long key = ((long long)a.count[g0 + h] << 32) | (long long)(0x7fffffff - h);
-        best = key > best ? key : best;
-        cert += a.status[g0 + h] == 0 ? 1 : 0;
-    }
-    for (int o = 32; o > 0; o >>= 1) {
-        const long long ob = __shfl_down(best, o);
-        best = ob > best ? ob : best;
-        cert += __shfl_down(cert, o);
-    }
-    if ((threadIdx.x & 63) == 0) { best_w[threadIdx.x >> 6] = best; cert_w[threadIdx.x >> 6] = cert; }
-    __syncthreads();
-    best = best_w[0]; cert = cert_w[0];
-#pragma unroll
-    for (int wv = 1; wv < WAVES; ++wv) { best = best_w[wv] > best ? best_w[wv] : best; cert += cert_w[wv]; }
-    int hb = (int)(0x7fffffffLL - (best & 0xffffffffLL));
-    hb = hb < 0 || hb >= a.n_hyp ? 0 : hb; // (a negative count cannot win; a corrupt one must not index outside the scene's hypotheses)
+    const cvxn::Winner w = cvxn::block_argmax<int64_t>(a.count, a.status, g0, a.n_hyp, best_w, cert_w);
+    const int hb = w.h, cert = w.cert;
     const int64_t gb = g0 + hb;
     const Scene sc = scene_of(a.s, f);
     Camera cam;
     cvxn::camera_load(a.R + gb * 9, a.t + gb * 3, sc.K, cam);
     const int n_inl = block_inliers(cam, sc, a.thresh, a.mask_p + sc.beg_p, a.mask_l + sc.beg_l, red);
-    if (threadIdx.x < 9) a.out_R[f * 9 + threadIdx.x] = a.R[gb * 9 + threadIdx.x];
-    if (threadIdx.x < 3) a.out_t[f * 3 + threadIdx.x] = a.t[gb * 3 + threadIdx.x];
+    cvxn::take_pose(a.R, a.t, gb, a.out_R, a.out_t, f);
     if (threadIdx.x == 0) { a.head[f * 4] = a.status[gb]; a.head[f * 4 + 1] = n_inl; a.head[f * 4 + 2] = hb; a.head[f * 4 + 3] = cert; }
 }
 
@@ -252,7 +229,7 @@ struct RefitArgs {
 };
 __global__ void __launch_bounds__(BLOCK) refit_update_kernel(RefitArgs a)
 {
-    __shared__ int red[WAVES];
+    __shared__ int red[SCENE_WAVES];
     const int64_t f = blockIdx.x;
     if (f >= a.s.n_scenes) return;
     const Scene sc = scene_of(a.s, f);
