@@ -47,116 +47,78 @@ class LibraryMissing(RuntimeError):
 _loaded = {}
 
 
-def _load(path, exports, set_argtypes):
+def _load(path, exports, set_argtypes, missing=None, optional=()):
     """Load a library of `exports` once (loudly).  Every export returns int but *_last_error and *_version, which return a string;
-    set_argtypes(L) gives the argument types, and the return type of an export that returns something else."""
+    set_argtypes(L) gives the argument types, and the return type of an export that returns something else.  missing: the message of a
+    library that is not there; optional: exports the library may lack."""
     L = _loaded.get(path)
     if L is None:
         if not os.path.exists(path):
-            raise LibraryMissing(f"{path} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
+            raise LibraryMissing(missing or f"{path} is missing: the HIP extension has not been built (`python -m cvxpnpl_amd.build`)")
         L = C.CDLL(path)
         for name in exports:
-            getattr(L, name).restype = C.c_char_p if name.endswith(("_last_error", "_version")) else C.c_int
+            if name not in optional or hasattr(L, name):
+                getattr(L, name).restype = C.c_char_p if name.endswith(("_last_error", "_version")) else C.c_int
         set_argtypes(L)
         _loaded[path] = L
     return L
 
 
-_lib = None
+# an A/B library of an earlier round, loaded through the diagnostics variable, may predate these entries; the product library must have them
+_SOLVER_OPTIONAL = ("cvxpnpl_stream_wait_value_bounded", "cvxpnpl_stream_wait_gave_up", "cvxpnpl_select_best", "cvxpnpl_refit_update",
+                    "cvxpnpl_last_layout")
+
+
+def _solver_argtypes(L):
+    p, i32, i64, u64, f64, size = C.c_void_p, C.c_int32, C.c_int64, C.c_uint64, C.c_double, C.c_size_t
+    corr = [i64, i32, p, p, i32, p, p, p, i32]  # batch, n_p, pts_2d, pts_3d, n_l, line_2d, line_3d, K, K_per_problem
+    outs = [p, p, p, p, p, p, p]                # R, t, status, iters, cost, Z, work
+    argtypes = {
+        "cvxpnpl_default_opts": [C.POINTER(Opts)], "cvxpnpl_opts_size": [],
+        "cvxpnpl_solve_batch": corr + [C.POINTER(Opts)] + outs + [p],
+        "cvxpnpl_solve_cost_batch": [i64, p, p, C.POINTER(Opts)] + outs + [p],
+        "cvxpnpl_assemble_batch": corr + [p, p, p],
+        "cvxpnpl_assemble_large_scratch_bytes": [i64, i32, i32],
+        "cvxpnpl_assemble_large_batch": corr + [p, p, p, size, p],
+        "cvxpnpl_recover_multi": [_dp, _dp, _dp, _dp, _dp],
+        "cvxpnpl_recover_multi_batch": [i64, _ip, _dp, _dp, _dp, _dp, _dp, _ip, i32],
+        "cvxpnpl_recover_multi_device": [i64, p, p, p, p, p, p, p, p],
+        "cvxpnpl_pack_results": [i64, p, p, p, p, p],
+        "cvxpnpl_stream_write_value": [p, u64, p], "cvxpnpl_stream_wait_value": [p, u64, p],
+        "cvxpnpl_stream_wait_value_bounded": [p, u64, u64, p], "cvxpnpl_stream_wait_gave_up": [p, i32, p],
+        "cvxpnpl_score_hypotheses": [i64, p, p, p, C.c_uint32, p, i32, p, p, f64, p, p, p],
+        "cvxpnpl_select_best": [i64, p, p, p, p, p, i32, p, p, f64, p, p, p, p, p],
+        "cvxpnpl_refit_update": [p, p, p, p, p, i32, p, p, f64, p, p, p, p, p],
+        "cvxpnpl_sample_minimal_sets": [i64, i32, p, p, i32, u64, p, p, p, p],
+        "cvxpnpl_synth_batch": [i64, i32, i32, f64, u64, p, p, p, p, p, p, p, p],
+        "cvxpnpl_pose_errors": [i64, p, p, p, p, p, p, p],
+        "cvxpnpl_disambiguate": [i64, p, p, p, p, p, p, p, i32, p, p, p, p],
+        "cvxpnpl_workspace_bytes": [i64], "cvxpnpl_set_workspace": [p, size, p], "cvxpnpl_release_workspace": [p, i32],
+        "cvxpnpl_calibration_copy": [p, p, i64, i32, p],
+        "cvxpnpl_assemble_subsets": [i64, i32, p, p, p, p, p, p, p, p],
+        "cvxpnpl_ipm_batch": [i64, p, i32, p, p, p, p, p],
+        "cvxpnpl_event_record": [p, p], "cvxpnpl_event_elapsed_ms": [p, p, C.POINTER(C.c_float)], "cvxpnpl_event_destroy": [p],
+    }
+    for name, types in argtypes.items():
+        if name not in _SOLVER_OPTIONAL or hasattr(L, name):
+            getattr(L, name).argtypes = types
+    L.cvxpnpl_default_opts.restype = L.cvxpnpl_event_destroy.restype = None
+    L.cvxpnpl_opts_size.restype = L.cvxpnpl_assemble_large_scratch_bytes.restype = L.cvxpnpl_workspace_bytes.restype = size
+    L.cvxpnpl_event_create.restype = p
+    if L.cvxpnpl_opts_size() != C.sizeof(Opts):  # the hand-written mirror above and the header must move in lock-step
+        raise ImportError(f"cvxpnpl_amd._lib.Opts has {C.sizeof(Opts)} bytes, {LIB_PATH} expects {L.cvxpnpl_opts_size()} (include/cvxpnpl_amd.h)")
 
 
 def lib():
     """Load libcvxpnpl_amd.so (loudly)."""
-    global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise LibraryMissing(
-            f"{LIB_PATH} is missing: the HIP extension has not been built "
-            "(run `python -c 'import __graft_entry__ as g; g.build()'` or `python -m cvxpnpl_amd.build`). "
-            "cvxpnpl_amd has no CPU fallback.")
-    L = C.CDLL(LIB_PATH)
-    L.cvxpnpl_default_opts.argtypes = [C.POINTER(Opts)]
-    L.cvxpnpl_default_opts.restype = None
-    L.cvxpnpl_opts_size.argtypes = []
-    L.cvxpnpl_opts_size.restype = C.c_size_t
-    if L.cvxpnpl_opts_size() != C.sizeof(Opts):  # the hand-written mirror above and the header must move in lock-step
-        raise ImportError(f"cvxpnpl_amd._lib.Opts has {C.sizeof(Opts)} bytes, {LIB_PATH} expects {L.cvxpnpl_opts_size()} (include/cvxpnpl_amd.h)")
-    L.cvxpnpl_solve_batch.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_int32, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_solve_batch.restype = C.c_int
-    L.cvxpnpl_solve_cost_batch.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.POINTER(Opts), C.c_void_p, C.c_void_p, C.c_void_p,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_solve_cost_batch.restype = C.c_int
-    L.cvxpnpl_assemble_batch.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                         C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_assemble_batch.restype = C.c_int
-    L.cvxpnpl_assemble_large_scratch_bytes.argtypes = [C.c_int64, C.c_int32, C.c_int32]
-    L.cvxpnpl_assemble_large_scratch_bytes.restype = C.c_size_t
-    L.cvxpnpl_assemble_large_batch.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
-    L.cvxpnpl_assemble_large_batch.restype = C.c_int
-    L.cvxpnpl_recover_multi.argtypes = [_dp, _dp, _dp, _dp, _dp]
-    L.cvxpnpl_recover_multi.restype = C.c_int
-    L.cvxpnpl_recover_multi_batch.argtypes = [C.c_int64, _ip, _dp, _dp, _dp, _dp, _dp, _ip, C.c_int32]
-    L.cvxpnpl_recover_multi_batch.restype = C.c_int
-    L.cvxpnpl_recover_multi_device.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_recover_multi_device.restype = C.c_int
-    L.cvxpnpl_pack_results.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_pack_results.restype = C.c_int
-    L.cvxpnpl_stream_write_value.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    L.cvxpnpl_stream_write_value.restype = C.c_int
-    L.cvxpnpl_stream_wait_value.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p]
-    L.cvxpnpl_stream_wait_value.restype = C.c_int
-    if not os.environ.get("CVXPNPL_AMD_LIB") or hasattr(L, "cvxpnpl_stream_wait_value_bounded"):  # (an A/B library of an earlier round, loaded
-        # through the diagnostics variable, may predate these two entries; the product library must have them)
-        L.cvxpnpl_stream_wait_value_bounded.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p]
-        L.cvxpnpl_stream_wait_value_bounded.restype = C.c_int
-        L.cvxpnpl_stream_wait_gave_up.argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
-        L.cvxpnpl_stream_wait_gave_up.restype = C.c_int
-    L.cvxpnpl_score_hypotheses.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32,
-                                           C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_score_hypotheses.restype = C.c_int
-    if not os.environ.get("CVXPNPL_AMD_LIB") or hasattr(L, "cvxpnpl_select_best"):  # (an A/B library of an earlier round lacks them)
-        L.cvxpnpl_select_best.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
-                                          C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvxpnpl_select_best.restype = C.c_int
-        L.cvxpnpl_refit_update.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double,
-                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.cvxpnpl_refit_update.restype = C.c_int
-    L.cvxpnpl_sample_minimal_sets.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_sample_minimal_sets.restype = C.c_int
-    L.cvxpnpl_synth_batch.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_synth_batch.restype = C.c_int
-    L.cvxpnpl_pose_errors.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_pose_errors.restype = C.c_int
-    L.cvxpnpl_disambiguate.argtypes = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_disambiguate.restype = C.c_int
-    L.cvxpnpl_workspace_bytes.argtypes = [C.c_int64]
-    L.cvxpnpl_workspace_bytes.restype = C.c_size_t
-    L.cvxpnpl_set_workspace.argtypes = [C.c_void_p, C.c_size_t, C.c_void_p]
-    L.cvxpnpl_set_workspace.restype = C.c_int
-    L.cvxpnpl_release_workspace.argtypes = [C.c_void_p, C.c_int32]
-    L.cvxpnpl_release_workspace.restype = C.c_int
-    L.cvxpnpl_calibration_copy.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p]
-    L.cvxpnpl_calibration_copy.restype = C.c_int
-    L.cvxpnpl_assemble_subsets.argtypes = [C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_assemble_subsets.restype = C.c_int
-    L.cvxpnpl_ipm_batch.argtypes = [C.c_int64, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    L.cvxpnpl_ipm_batch.restype = C.c_int
-    L.cvxpnpl_event_create.restype = C.c_void_p
-    L.cvxpnpl_event_record.argtypes = [C.c_void_p, C.c_void_p]
-    L.cvxpnpl_event_elapsed_ms.argtypes = [C.c_void_p, C.c_void_p, C.POINTER(C.c_float)]
-    L.cvxpnpl_event_destroy.argtypes = [C.c_void_p]
-    L.cvxpnpl_event_destroy.restype = None
-    L.cvxpnpl_last_error.restype = C.c_char_p
-    L.cvxpnpl_version.restype = C.c_char_p
-    L.cvxpnpl_device_count.restype = C.c_int
-    _lib = L
-    return L
+    L = _loaded.get(LIB_PATH)  # (every pnp() call comes through here: no message is formatted once the library is loaded)
+    if L is not None:
+        return L
+    return _load(LIB_PATH, EXPORTS, _solver_argtypes,
+                 missing=f"{LIB_PATH} is missing: the HIP extension has not been built "
+                 "(run `python -c 'import __graft_entry__ as g; g.build()'` or `python -m cvxpnpl_amd.build`). "
+                 "cvxpnpl_amd has no CPU fallback.",
+                 optional=_SOLVER_OPTIONAL if os.environ.get("CVXPNPL_AMD_LIB") else ())
 
 
 # the backward pass (include/cvxpnpl_amd_grad.h): a library of its own beside the solver's

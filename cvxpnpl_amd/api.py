@@ -72,6 +72,67 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None and t.numel() > 0 else C.c_void_p(0)
 
 
+# ---- the plumbing of a call into the solver library (metrics.py, synth.py, dist.py and grad.py use it too) ----
+
+def _device_of(device, *tensors):
+    """The device rule: `device` when given, else that of the first CUDA tensor among `tensors`, else the current device."""
+    if device is not None:
+        return torch.device(device)
+    for a in tensors:
+        if isinstance(a, torch.Tensor) and a.is_cuda:
+            return a.device
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _stream(device):
+    """The current stream of `device` as the C entry points take it."""
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _call(L, name, *args, last_error="cvxpnpl_last_error"):
+    """Entry point `name` of the library L; a failure raises with the message of the library's `last_error`."""
+    rc = getattr(L, name)(*args)
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {getattr(L, last_error)().decode()}")
+
+
+def _alloc_result(batch, device, want_Z):
+    """The outputs of a solve, uninitialised: the BatchResult (Z when wanted) and its pointers in the order of the C entry points."""
+    f64, i32 = dict(dtype=torch.float64, device=device), dict(dtype=torch.int32, device=device)
+    out = BatchResult(R=torch.empty((batch, 3, 3), **f64), t=torch.empty((batch, 3), **f64), status=torch.empty((batch,), **i32),
+                      iters=torch.empty((batch,), **i32), cost=torch.empty((batch, 2), **f64), work=torch.empty((batch, 2), **i32))
+    if want_Z:
+        out["Z"] = torch.empty((batch, 55), **f64)
+    return out, (_ptr(out.R), _ptr(out.t), _ptr(out.status), _ptr(out.iters), _ptr(out.cost), _ptr(out.get("Z")), _ptr(out.work))
+
+
+# ---- the head of pnpl_batch and assemble_batch: the same checks, each function in its own order ----
+
+def _head_3d(pts_3d, line_3d, device):
+    """The 3D halves on the device and the shape of the batch they describe: (p3, l3, n_p, n_l, batch)."""
+    p3 = _as_dev(pts_3d, device, (3,)) if pts_3d is not None else None
+    l3 = _as_dev(line_3d, device, (2, 3)) if line_3d is not None else None
+    n_p = p3.shape[-2] if p3 is not None and p3.dim() >= 3 else 0
+    n_l = l3.shape[-3] if l3 is not None and l3.dim() >= 4 else 0
+    if n_p == 0 and n_l == 0:
+        raise ValueError("need at least one point or line correspondence ([B,n,3] points / [B,n,2,3] lines)")
+    return p3, l3, n_p, n_l, (p3 if n_p else l3).shape[0]
+
+
+def _chk_one_batch(l3, n_p, n_l, batch):
+    if n_p and n_l and l3.shape[0] != batch:
+        raise ValueError(f"points and lines describe different batches ({batch} vs {l3.shape[0]})")
+
+
+def _K_dev(K, device, batch):
+    """K on the device, [3,3] or [batch,3,3] (a short [m,3,3] would be read out of bounds by the kernels): (K, 1 when per problem)."""
+    Kd = _as_dev(K, device, (3, 3))
+    per = int(Kd.dim() == 3)
+    if Kd.dim() not in (2, 3) or (per and Kd.shape[0] != batch):
+        raise ValueError("K must be [3,3] or [batch,3,3]")
+    return Kd, per
+
+
 def pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, eps: float = 1e-9, max_iters: int = 2500, want_Z: bool = False,
                device=None, **solver_opts) -> BatchResult:
     """Solve B independent PnPL problems of identical shape on the GPU.
@@ -82,27 +143,10 @@ def pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, eps: float = 1e-9, max_iters
     """
     _require_gpu()
     L = _lib.lib()
-    if device is None:
-        for a in (pts_3d, line_3d, pts_2d, line_2d):
-            if isinstance(a, torch.Tensor) and a.is_cuda:
-                device = a.device
-                break
-        else:
-            device = torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
-    p3 = _as_dev(pts_3d, device, (3,)) if pts_3d is not None else None
-    l3 = _as_dev(line_3d, device, (2, 3)) if line_3d is not None else None
-    n_p = p3.shape[-2] if p3 is not None and p3.dim() >= 3 else 0
-    n_l = l3.shape[-3] if l3 is not None and l3.dim() >= 4 else 0
-    if n_p == 0 and n_l == 0:
-        raise ValueError("need at least one point or line correspondence ([B,n,3] points / [B,n,2,3] lines)")
-    batch = (p3 if n_p else l3).shape[0]
-    if n_p and n_l and l3.shape[0] != batch:
-        raise ValueError(f"points and lines describe different batches ({batch} vs {l3.shape[0]})")
-    Kd = _as_dev(K, device, (3, 3))
-    per = int(Kd.dim() == 3)
-    if Kd.dim() not in (2, 3) or (per and Kd.shape[0] != batch):
-        raise ValueError("K must be [3,3] or [batch,3,3]")
+    device = _device_of(device, pts_3d, line_3d, pts_2d, line_2d)
+    p3, l3, n_p, n_l, batch = _head_3d(pts_3d, line_3d, device)
+    _chk_one_batch(l3, n_p, n_l, batch)
+    Kd, per = _K_dev(K, device, batch)
     if batch > 0 and use_blocked_assembly(n_p + 2 * n_l, batch):
         # the scalability regime (benchmarks/scalability/pnp.py:37-40: up to 10^4 points per problem): bandwidth-shaped
         # blocked assembly, then the solve at the cost seam -- instead of one wavefront streaming the problem
@@ -113,16 +157,8 @@ def pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, eps: float = 1e-9, max_iters
     l3 = l3.reshape(batch, n_l, 2, 3) if n_l else None
     opts = _lib.default_opts(eps=float(eps), max_iters=int(max_iters), **solver_opts)
     with torch.cuda.device(device):
-        R, t, status, iters, cost, work, Z = _alloc_outputs(batch, device, want_Z)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        rc = L.cvxpnpl_solve_batch(batch, n_p, _ptr(p2), _ptr(p3), n_l, _ptr(l2), _ptr(l3), _ptr(Kd), per, C.byref(opts),
-                                   _ptr(R), _ptr(t), _ptr(status), _ptr(iters), _ptr(cost), _ptr(Z), _ptr(work),
-                                   C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_solve_batch failed ({rc}): {_lib.last_error()}")
-    out = BatchResult(R=R, t=t, status=status, iters=iters, cost=cost, work=work)
-    if want_Z:
-        out["Z"] = Z
+        out, outs = _alloc_result(batch, device, want_Z)
+        _call(L, "cvxpnpl_solve_batch", batch, n_p, _ptr(p2), _ptr(p3), n_l, _ptr(l2), _ptr(l3), _ptr(Kd), per, C.byref(opts), *outs, _stream(device))
     return out
 
 
@@ -197,22 +233,8 @@ def recover_multi_device(res: "BatchResult", B, Q=None):
         R = torch.empty((n, 4, 3, 3), dtype=torch.float64, device=dev)
         t = torch.empty((n, 4, 3), dtype=torch.float64, device=dev)
         cnt = torch.empty((n,), dtype=torch.int32, device=dev)
-        rc = L.cvxpnpl_recover_multi_device(n, _ptr(st), _ptr(Z), _ptr(Bd), _ptr(Qd), _ptr(R), _ptr(t), _ptr(cnt),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_recover_multi_device failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_recover_multi_device", n, _ptr(st), _ptr(Z), _ptr(Bd), _ptr(Qd), _ptr(R), _ptr(t), _ptr(cnt), _stream(dev))
     return R, t, cnt
-
-
-def _alloc_outputs(batch, device, want_Z):
-    R = torch.empty((batch, 3, 3), dtype=torch.float64, device=device)
-    t = torch.empty((batch, 3), dtype=torch.float64, device=device)
-    status = torch.empty((batch,), dtype=torch.int32, device=device)
-    iters = torch.empty((batch,), dtype=torch.int32, device=device)
-    cost = torch.empty((batch, 2), dtype=torch.float64, device=device)
-    work = torch.empty((batch, 2), dtype=torch.int32, device=device)
-    Z = torch.empty((batch, 55), dtype=torch.float64, device=device) if want_Z else None
-    return R, t, status, iters, cost, work, Z
 
 
 _IU9 = np.triu_indices(9)
@@ -231,9 +253,7 @@ def solve_cost_batch(Q45, B27, eps: float = 1e-9, max_iters: int = 2500, want_Z:
     correspondences.  variant=VARIANT_RC solves the reference's 16-equality ablation (benchmarks/toolkit/methods/rc.py)."""
     _require_gpu()
     L = _lib.lib()
-    if device is None:
-        device = Q45.device if isinstance(Q45, torch.Tensor) and Q45.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = _device_of(device, Q45)
     Qd = _as_dev(Q45, device, (45,))
     batch = Qd.shape[0] if Qd.dim() == 2 else 1
     Qd = Qd.reshape(batch, 45)
@@ -244,15 +264,8 @@ def solve_cost_batch(Q45, B27, eps: float = 1e-9, max_iters: int = 2500, want_Z:
     Bd = Bd.reshape(batch, 27)
     opts = _lib.default_opts(eps=float(eps), max_iters=int(max_iters), variant=int(variant), **solver_opts)
     with torch.cuda.device(device):
-        R, t, status, iters, cost, work, Z = _alloc_outputs(batch, device, want_Z)
-        stream = torch.cuda.current_stream(device).cuda_stream
-        rc = L.cvxpnpl_solve_cost_batch(batch, _ptr(Qd), _ptr(Bd), C.byref(opts), _ptr(R), _ptr(t), _ptr(status), _ptr(iters),
-                                        _ptr(cost), _ptr(Z), _ptr(work), C.c_void_p(stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_solve_cost_batch failed ({rc}): {_lib.last_error()}")
-    out = BatchResult(R=R, t=t, status=status, iters=iters, cost=cost, work=work)
-    if want_Z:
-        out["Z"] = Z
+        out, outs = _alloc_result(batch, device, want_Z)
+        _call(L, "cvxpnpl_solve_cost_batch", batch, _ptr(Qd), _ptr(Bd), C.byref(opts), *outs, _stream(device))
     return out
 
 
@@ -263,9 +276,7 @@ def ipm_batch(Q45, variant: int = _lib.VARIANT_FULL, device=None):
     No rounding, polish or certificate: what opts.rescue_from runs for a slow problem before the first-order iteration takes over again."""
     _require_gpu()
     L = _lib.lib()
-    if device is None:
-        device = Q45.device if isinstance(Q45, torch.Tensor) and Q45.is_cuda else torch.device("cuda", torch.cuda.current_device())
-    device = torch.device(device)
+    device = _device_of(device, Q45)
     Qd = _as_dev(Q45, device, (45,)).reshape(-1, 45)
     batch = Qd.shape[0]
     di = torch.as_tensor(np.flatnonzero(_IU9[0] == _IU9[1]), device=device)
@@ -279,9 +290,7 @@ def ipm_batch(Q45, variant: int = _lib.VARIANT_FULL, device=None):
         S = torch.empty((batch, 10, 10), dtype=torch.float64, device=device)
         gap = torch.empty((batch,), dtype=torch.float64, device=device)
         iters = torch.empty((batch,), dtype=torch.int32, device=device)
-        rc = L.cvxpnpl_ipm_batch(batch, _ptr(Qs), int(variant), _ptr(Z), _ptr(S), _ptr(gap), _ptr(iters), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_ipm_batch failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_ipm_batch", batch, _ptr(Qs), int(variant), _ptr(Z), _ptr(S), _ptr(gap), _ptr(iters), _stream(device))
     return Z, S, gap, iters  # (iters: iterations | reason << 8, see cvxpnpl_ipm_batch)
 
 
@@ -316,7 +325,7 @@ class _SingleCtx:
 
     N_OUT = 9 + 3 + 2 + 55  # R, t, cost | dobj, Z (doubles); then status, iters, work[2] as int32 in two more doubles
 
-    def __init__(self, device, n_p, n_l):
+    def __init__(self, L, device, n_p, n_l):
         self.n_p, self.n_l = n_p, n_l
         # (n_p = -1: the cost seam -- [Q45 | B27] instead of correspondences and K)
         self.sizes = (2 * n_p, 3 * n_p, 4 * n_l, 6 * n_l, 9) if n_p >= 0 else (45, 27, 0, 0, 0)
@@ -330,93 +339,66 @@ class _SingleCtx:
         self.o_np = self.h_out.numpy()
         self.i_np = self.o_np[self.N_OUT:].view(np.int32)
         base_in, base_out = self.d_in.data_ptr(), self.d_out.data_ptr()
-        pin = [C.c_void_p(base_in + 8 * int(o)) if sz else C.c_void_p(0) for o, sz in zip(self.offs[:-1], self.sizes)]
-        self.p2, self.p3, self.l2, self.l3, self.K = pin
+        self.slots = [slice(int(lo), int(hi)) for lo, hi in zip(self.offs[:-1], self.offs[1:])]  # of h_np, one per entry of sizes
+        p2, p3, l2, l3, K = [C.c_void_p(base_in + 8 * sl.start) if sz else C.c_void_p(0) for sl, sz in zip(self.slots, self.sizes)]
         o = lambda k: C.c_void_p(base_out + 8 * k)  # noqa: E731
-        self.R, self.t, self.cost, self.Z = o(0), o(9), o(12), o(14)
-        self.status, self.iters, self.work = o(self.N_OUT), C.c_void_p(base_out + 8 * self.N_OUT + 4), C.c_void_p(base_out + 8 * self.N_OUT + 8)
+        i = lambda k: C.c_void_p(base_out + 8 * self.N_OUT + 4 * k)  # noqa: E731
+        # the call, around the options: the entry point, its arguments before them, and R, t, status, iters, cost, Z, work after them
+        self.entry = L.cvxpnpl_solve_batch if n_p >= 0 else L.cvxpnpl_solve_cost_batch
+        self.head = (1, n_p, p2, p3, n_l, l2, l3, K, 0) if n_p >= 0 else (1, p2, p3)
+        self.outs = (o(0), o(9), i(0), i(1), o(12), o(14), i(2))
 
 
 _single_tls = threading.local()
 
 
-def _single_fast(p2, l2, p3, l3, Kn, eps, max_iters):
-    """One problem through the staging of _SingleCtx; the outputs as a BatchResult of host tensors (batch 1)."""
+def _single_staged(n_p, n_l, parts, eps, max_iters, variant=None):
+    """One problem through the staging of _SingleCtx; the outputs as a BatchResult of host tensors (batch 1).  parts: the arrays of
+    _SingleCtx.sizes in their order, None for an empty one; n_p = -1 and a variant: the cost seam."""
     _require_gpu()
     L = _lib.lib()
     device = torch.device("cuda", torch.cuda.current_device())
-    n_p = 0 if p3 is None else p3.shape[1]
-    n_l = 0 if l3 is None else l3.shape[1]
     cache = getattr(_single_tls, "ctx", None)
     if cache is None:
         cache = _single_tls.ctx = {}
     key = (device.index, n_p, n_l)
     ctx = cache.get(key)
     if ctx is None:
-        if len(cache) > 64:
+        if n_p >= 0 and len(cache) > 64:  # (the shapes of the correspondence path are the caller's; the cost seam has one)
             cache.clear()
-        ctx = cache[key] = _SingleCtx(device, n_p, n_l)
-    h, of = ctx.h_np, ctx.offs
-    if n_p:
-        h[of[0]:of[1]] = p2.reshape(-1)
-        h[of[1]:of[2]] = p3.reshape(-1)
-    if n_l:
-        h[of[2]:of[3]] = l2.reshape(-1)
-        h[of[3]:of[4]] = l3.reshape(-1)
-    h[of[4]:of[5]] = Kn.reshape(-1)
-    okey = (float(eps), int(max_iters))
-    opts = getattr(_single_tls, "opts", {}).get(okey)
+        ctx = cache[key] = _SingleCtx(L, device, n_p, n_l)
+    h = ctx.h_np
+    for sl, part in zip(ctx.slots, parts):
+        if part is not None:
+            h[sl] = part.reshape(-1)
+    okey = (float(eps), int(max_iters)) if variant is None else (float(eps), int(max_iters), int(variant))
+    if not hasattr(_single_tls, "opts"):
+        _single_tls.opts = {}
+    opts = _single_tls.opts.get(okey)
     if opts is None:
-        if not hasattr(_single_tls, "opts"):
-            _single_tls.opts = {}
-        opts = _single_tls.opts[okey] = _lib.default_opts(eps=float(eps), max_iters=int(max_iters), res_tol=0.0)
+        opts = _single_tls.opts[okey] = _lib.default_opts(eps=float(eps), max_iters=int(max_iters), res_tol=0.0, variant=variant if variant is None else int(variant))
     with torch.cuda.device(device):
         stream = torch.cuda.current_stream(device)
         ctx.d_in.copy_(ctx.h_in, non_blocking=True)
-        rc = L.cvxpnpl_solve_batch(1, n_p, ctx.p2, ctx.p3, n_l, ctx.l2, ctx.l3, ctx.K, 0, C.byref(opts), ctx.R, ctx.t, ctx.status, ctx.iters, ctx.cost, ctx.Z,
-                                   ctx.work, C.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"cvxpnpl_solve_batch failed ({rc}): {_lib.last_error()}")
+        rc = ctx.entry(*ctx.head, C.byref(opts), *ctx.outs, C.c_void_p(stream.cuda_stream))
+        if rc != 0:  # (_call, written out: this is the single-call path, the one figure the reference itself would time)
+            raise RuntimeError(f"{ctx.entry.__name__} failed ({rc}): {_lib.last_error()}")
         ctx.h_out.copy_(ctx.d_out, non_blocking=True)
         stream.synchronize()
     o, i = ctx.o_np, ctx.i_np
     return BatchResult(R=torch.from_numpy(o[0:9].reshape(1, 3, 3).copy()), t=torch.from_numpy(o[9:12].reshape(1, 3).copy()),
                        status=torch.from_numpy(i[0:1].copy()), iters=torch.from_numpy(i[1:2].copy()), cost=torch.from_numpy(o[12:14].reshape(1, 2).copy()),
                        work=torch.from_numpy(i[2:4].reshape(1, 2).copy()), Z=torch.from_numpy(o[14:69].reshape(1, 55).copy()))
+
+
+def _single_fast(p2, l2, p3, l3, Kn, eps, max_iters):
+    """One problem given as correspondences (pnp / pnl / pnpl)."""
+    return _single_staged(0 if p3 is None else p3.shape[1], 0 if l3 is None else l3.shape[1], (p2, p3, l2, l3, Kn), eps, max_iters)
 
 
 def _single_cost_fast(Q45, B27, eps, max_iters, variant):
     """The same staging for the cost seam (solve_relaxation / solve_relaxation_rc: one problem given as packed A^T A and B)."""
-    _require_gpu()
-    L = _lib.lib()
-    device = torch.device("cuda", torch.cuda.current_device())
-    cache = getattr(_single_tls, "ctx", None)
-    if cache is None:
-        cache = _single_tls.ctx = {}
-    key = (device.index, -1, 0)
-    ctx = cache.get(key)
-    if ctx is None:
-        ctx = cache[key] = _SingleCtx(device, -1, 0)
-    ctx.h_np[0:45] = Q45
-    ctx.h_np[45:72] = B27
-    if not hasattr(_single_tls, "opts"):
-        _single_tls.opts = {}
-    okey = (float(eps), int(max_iters), int(variant))
-    opts = _single_tls.opts.get(okey)
-    if opts is None:
-        opts = _single_tls.opts[okey] = _lib.default_opts(eps=float(eps), max_iters=int(max_iters), res_tol=0.0, variant=int(variant))
-    with torch.cuda.device(device):
-        stream = torch.cuda.current_stream(device)
-        ctx.d_in.copy_(ctx.h_in, non_blocking=True)
-        rc = L.cvxpnpl_solve_cost_batch(1, ctx.p2, ctx.p3, C.byref(opts), ctx.R, ctx.t, ctx.status, ctx.iters, ctx.cost, ctx.Z, ctx.work, C.c_void_p(stream.cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"cvxpnpl_solve_cost_batch failed ({rc}): {_lib.last_error()}")
-        ctx.h_out.copy_(ctx.d_out, non_blocking=True)
-        stream.synchronize()
-    o, i = ctx.o_np, ctx.i_np
-    return BatchResult(R=torch.from_numpy(o[0:9].reshape(1, 3, 3).copy()), t=torch.from_numpy(o[9:12].reshape(1, 3).copy()),
-                       status=torch.from_numpy(i[0:1].copy()), iters=torch.from_numpy(i[1:2].copy()), cost=torch.from_numpy(o[12:14].reshape(1, 2).copy()),
-                       work=torch.from_numpy(i[2:4].reshape(1, 2).copy()), Z=torch.from_numpy(o[14:69].reshape(1, 55).copy()))
+    return _single_staged(-1, 0, (Q45, B27), eps, max_iters, variant)
 
 
 def _single(pts_2d, line_2d, pts_3d, line_3d, K, eps, max_iters, verbose) -> List[Tuple[np.ndarray, np.ndarray]]:
@@ -489,21 +471,11 @@ def assemble_batch(pts_2d, line_2d, pts_3d, line_3d, K, device=None, blocked=Non
     the rank > 1 recovery (recover_multi) needs next to Z."""
     _require_gpu()
     L = _lib.lib()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    p3 = _as_dev(pts_3d, dev, (3,)) if pts_3d is not None else None
-    l3 = _as_dev(line_3d, dev, (2, 3)) if line_3d is not None else None
-    n_p = p3.shape[-2] if p3 is not None and p3.dim() >= 3 else 0
-    n_l = l3.shape[-3] if l3 is not None and l3.dim() >= 4 else 0
-    if n_p == 0 and n_l == 0:
-        raise ValueError("need at least one point or line correspondence ([B,n,3] points / [B,n,2,3] lines)")
-    batch = (p3 if n_p else l3).shape[0]
+    dev = _device_of(device)
+    p3, l3, n_p, n_l, batch = _head_3d(pts_3d, line_3d, dev)
     p2, l2 = _pair_2d(pts_2d, line_2d, dev, batch, n_p, n_l)
-    Kd = _as_dev(K, dev, (3, 3))
-    per = int(Kd.dim() == 3)
-    if Kd.dim() not in (2, 3) or (per and Kd.shape[0] != batch):  # (a short [m,3,3] would be read out of bounds by the kernels)
-        raise ValueError("K must be [3,3] or [batch,3,3]")
-    if n_p and n_l and l3.shape[0] != batch:
-        raise ValueError(f"points and lines describe different batches ({batch} vs {l3.shape[0]})")
+    Kd, per = _K_dev(K, dev, batch)
+    _chk_one_batch(l3, n_p, n_l, batch)
     if blocked is None:
         blocked = use_blocked_assembly(n_p + 2 * n_l, batch)
     p3 = p3.reshape(batch, n_p, 3) if n_p else None
@@ -511,7 +483,7 @@ def assemble_batch(pts_2d, line_2d, pts_3d, line_3d, K, device=None, blocked=Non
     with torch.cuda.device(dev):
         Bt = torch.empty((batch, 27), dtype=torch.float64, device=dev)
         Qt = torch.empty((batch, 45), dtype=torch.float64, device=dev)
-        sh = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        sh = _stream(dev)
         if blocked:
             # many correspondences per problem: several workgroups per problem at HBM rate (cvxpnpl_assemble_large_batch)
             for lo in range(0, batch, 65535):
@@ -519,16 +491,11 @@ def assemble_batch(pts_2d, line_2d, pts_3d, line_3d, K, device=None, blocked=Non
                 nb = L.cvxpnpl_assemble_large_scratch_bytes(hi - lo, n_p, n_l)
                 scratch = torch.empty((nb,), dtype=torch.uint8, device=dev)
                 sl = lambda x: None if x is None else x[lo:hi]  # noqa: E731
-                rc = L.cvxpnpl_assemble_large_batch(hi - lo, n_p, _ptr(sl(p2)), _ptr(sl(p3)), n_l, _ptr(sl(l2)), _ptr(sl(l3)),
-                                                    _ptr(Kd[lo:hi] if per else Kd), per, _ptr(Bt[lo:hi]), _ptr(Qt[lo:hi]),
-                                                    _ptr(scratch), nb, sh)
-                if rc != 0:
-                    raise RuntimeError(f"cvxpnpl_assemble_large_batch failed ({rc}): {_lib.last_error()}")
+                _call(L, "cvxpnpl_assemble_large_batch", hi - lo, n_p, _ptr(sl(p2)), _ptr(sl(p3)), n_l, _ptr(sl(l2)), _ptr(sl(l3)),
+                      _ptr(Kd[lo:hi] if per else Kd), per, _ptr(Bt[lo:hi]), _ptr(Qt[lo:hi]), _ptr(scratch), nb, sh)
             return Bt, Qt
-        rc = L.cvxpnpl_assemble_batch(batch, n_p, _ptr(p2), _ptr(p3 if n_p else None), n_l, _ptr(l2), _ptr(l3 if n_l else None),
-                                      _ptr(Kd), per, _ptr(Bt), _ptr(Qt), sh)
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_assemble_batch failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_assemble_batch", batch, n_p, _ptr(p2), _ptr(p3 if n_p else None), n_l, _ptr(l2), _ptr(l3 if n_l else None), _ptr(Kd), per,
+              _ptr(Bt), _ptr(Qt), sh)
     return Bt, Qt
 
 
@@ -540,7 +507,7 @@ def score_hypotheses(R, t, K, pts_2d, pts_3d, thresh: float = 2.0, status=None, 
     Returns count [H] int32, or (count, mask [H,M] uint8) with want_mask."""
     _require_gpu()
     L = _lib.lib()
-    dev = R.device if isinstance(R, torch.Tensor) and R.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(None, R)
     Rd = _as_dev(R, dev, (3, 3))
     td = _as_dev(t, dev, (3,))
     Kd = _as_dev(K, dev, (3, 3))
@@ -563,10 +530,8 @@ def score_hypotheses(R, t, K, pts_2d, pts_3d, thresh: float = 2.0, status=None, 
     with torch.cuda.device(dev):
         count = torch.empty((H,), dtype=torch.int32, device=dev)
         mask = torch.empty((H, M), dtype=torch.uint8, device=dev) if want_mask else None
-        rc = L.cvxpnpl_score_hypotheses(H, _ptr(Rd), _ptr(td), _ptr(st), um, _ptr(Kd), M, _ptr(x), _ptr(X), float(thresh),
-                                        _ptr(count), _ptr(mask), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_score_hypotheses failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_score_hypotheses", H, _ptr(Rd), _ptr(td), _ptr(st), um, _ptr(Kd), M, _ptr(x), _ptr(X), float(thresh), _ptr(count), _ptr(mask),
+              _stream(dev))
     return (count, mask) if want_mask else count
 
 
@@ -585,10 +550,8 @@ def select_best(count, R, t, status, K, pts_2d, pts_3d, thresh: float = 2.0):
         ot = torch.empty((1, 3), dtype=torch.float64, device=dev)
         head = torch.empty((4,), dtype=torch.int32, device=dev)
         mask = torch.empty((1, M), dtype=torch.uint8, device=dev)
-        rc = L.cvxpnpl_select_best(H, _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(K), M, _ptr(pts_2d), _ptr(pts_3d), float(thresh),
-                                   _ptr(oR), _ptr(ot), _ptr(head), _ptr(mask), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_select_best failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_select_best", H, _ptr(count), _ptr(R), _ptr(t), _ptr(status), _ptr(K), M, _ptr(pts_2d), _ptr(pts_3d), float(thresh),
+              _ptr(oR), _ptr(ot), _ptr(head), _ptr(mask), _stream(dev))
     return oR, ot, head, mask
 
 
@@ -598,10 +561,8 @@ def refit_update(fit: "BatchResult", fit_count, K, pts_2d, pts_3d, thresh, R, t,
     L = _lib.lib()
     dev = R.device
     with torch.cuda.device(dev):
-        rc = L.cvxpnpl_refit_update(_ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count), _ptr(K), pts_3d.shape[0], _ptr(pts_2d), _ptr(pts_3d),
-                                    float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_refit_update failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_refit_update", _ptr(fit.R), _ptr(fit.t), _ptr(fit.status), _ptr(fit_count), _ptr(K), pts_3d.shape[0], _ptr(pts_2d), _ptr(pts_3d),
+              float(thresh), _ptr(R), _ptr(t), _ptr(head), _ptr(mask), _stream(dev))
 
 
 def assemble_subsets(pts_2d, pts_3d, K, mask):
@@ -610,7 +571,7 @@ def assemble_subsets(pts_2d, pts_3d, K, mask):
     consensus set without a host round trip for its size."""
     _require_gpu()
     L = _lib.lib()
-    dev = mask.device if isinstance(mask, torch.Tensor) and mask.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(None, mask)
     x = _as_dev(pts_2d, dev, (2,)).reshape(-1, 2)
     X = _as_dev(pts_3d, dev, (3,)).reshape(-1, 3)
     Kd = _as_dev(K, dev, (3, 3)).reshape(3, 3)
@@ -623,9 +584,7 @@ def assemble_subsets(pts_2d, pts_3d, K, mask):
         Bt = torch.empty((Bn, 27), dtype=torch.float64, device=dev)
         Qt = torch.empty((Bn, 45), dtype=torch.float64, device=dev)
         cnt = torch.empty((Bn,), dtype=torch.int32, device=dev)
-        rc = L.cvxpnpl_assemble_subsets(Bn, M, _ptr(x), _ptr(X), _ptr(mk), _ptr(Kd), _ptr(Bt), _ptr(Qt), _ptr(cnt), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_assemble_subsets failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_assemble_subsets", Bn, M, _ptr(x), _ptr(X), _ptr(mk), _ptr(Kd), _ptr(Bt), _ptr(Qt), _ptr(cnt), _stream(dev))
     return Bt, Qt, cnt
 
 
@@ -637,7 +596,7 @@ def sample_minimal_sets(pts_2d, pts_3d, n_hyp: int, k: int = 4, seed: int = 0, w
     (p2, p3, idx [H,k] int32)."""
     _require_gpu()
     L = _lib.lib()
-    dev = pts_3d.device if isinstance(pts_3d, torch.Tensor) and pts_3d.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(None, pts_3d)
     x = _as_dev(pts_2d, dev, (2,))
     X = _as_dev(pts_3d, dev, (3,))
     if x.dim() != 2 or X.dim() != 2 or x.shape[0] != X.shape[0]:
@@ -649,10 +608,7 @@ def sample_minimal_sets(pts_2d, pts_3d, n_hyp: int, k: int = 4, seed: int = 0, w
         p2 = torch.empty((H, k, 2), dtype=torch.float64, device=dev)
         p3 = torch.empty((H, k, 3), dtype=torch.float64, device=dev)
         idx = torch.empty((H, k), dtype=torch.int32, device=dev) if want_idx else None
-        rc = L.cvxpnpl_sample_minimal_sets(H, M, _ptr(x), _ptr(X), int(k), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(idx), _ptr(p2), _ptr(p3),
-                                           C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_sample_minimal_sets failed ({rc}): {_lib.last_error()}")
+        _call(L, "cvxpnpl_sample_minimal_sets", H, M, _ptr(x), _ptr(X), int(k), int(seed) & 0xFFFFFFFFFFFFFFFF, _ptr(idx), _ptr(p2), _ptr(p3), _stream(dev))
     return (p2, p3, idx) if want_idx else (p2, p3)
 
 

@@ -9,13 +9,14 @@ SRC = os.path.join(HERE, "csrc", "cvxpnpl_hip.hip")
 HOST_SRC = os.path.join(HERE, "csrc", "host_recover.cpp")
 LANE_SRC = os.path.join(HERE, "csrc", "lane_kernel.hip")  # solve_lane2_kernel: a translation unit of its own (see its header)
 OUT = os.path.join(HERE, "libcvxpnpl_amd.so")
-DEPS = [SRC, HOST_SRC, LANE_SRC, os.path.join(HERE, "csrc", "batch_args.h"), os.path.join(HERE, "csrc", "launch_plan.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+ENTRY_ERROR_H = os.path.join(HERE, "csrc", "entry_error.h")  # the error text of every library's entry points
+SOLVER_ENTRY_HEADERS = [os.path.join(HERE, "csrc", "solver_entry.h"), ENTRY_ERROR_H]  # what the solver's and the pose VJP's entry files share
+DEPS = [SRC, HOST_SRC, LANE_SRC, *SOLVER_ENTRY_HEADERS, os.path.join(HERE, "csrc", "batch_args.h"), os.path.join(HERE, "csrc", "launch_plan.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
         os.path.join(HERE, "csrc", "wave_kernel.h"), os.path.join(HERE, "csrc", "quad_kernel.h"), os.path.join(HERE, "csrc", "score_kernel.h"), os.path.join(HERE, "csrc", "assemble_kernel.h"), os.path.join(HERE, "csrc", "synth_kernel.h"), os.path.join(HERE, "csrc", "recover_core.h"), os.path.join(HERE, "csrc", "recover_kernel.h"),
         os.path.join(HERE, "csrc", "ipm_core.h"), os.path.join(HERE, "csrc", "ipm_wave.h"), os.path.join(HERE, "csrc", "ipm_quad.h"), os.path.join(HERE, "csrc", "lane_core.h"),
         os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd.h")]
 
 
-ENTRY_ERROR_H = os.path.join(HERE, "csrc", "entry_error.h")  # the error text of the refinement and the RANSAC entry points
 RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the five RANSAC entry files share
 
 
@@ -44,7 +45,7 @@ GRAD_SRC = os.path.join(HERE, "csrc", "grad_hip.hip")
 GRAD_HOST_SRC = os.path.join(HERE, "csrc", "host_vjp.cpp")
 GRAD_OUT = os.path.join(HERE, "libcvxpnpl_amd_grad.so")
 GRAD_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_grad.resources.txt")
-GRAD_DEPS = [GRAD_SRC, GRAD_HOST_SRC, os.path.join(HERE, "csrc", "vjp_core.h"), os.path.join(HERE, "csrc", "vjp_kernel.h"), os.path.join(HERE, "csrc", "solver_core.h"),
+GRAD_DEPS = [GRAD_SRC, GRAD_HOST_SRC, *SOLVER_ENTRY_HEADERS, os.path.join(HERE, "csrc", "vjp_core.h"), os.path.join(HERE, "csrc", "vjp_kernel.h"), os.path.join(HERE, "csrc", "solver_core.h"),
              os.path.join(HERE, "csrc", "host_pool.h"),
              os.path.join(HERE, "csrc", "problem_io.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_grad.h")]
 

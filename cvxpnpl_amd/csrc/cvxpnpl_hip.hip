@@ -24,10 +24,15 @@
 #include "synth_kernel.h"
 #include "recover_kernel.h"
 #include "launch_plan.h"
+#include "solver_entry.h"
 
 namespace {
 
 using cvxb::BatchArgs; // (batch_args.h: shared with lane_kernel.hip)
+using cvxse::fail;      // (the error text, the correspondence block and the limit of one launch: solver_entry.h)
+using cvxse::hip_error;
+using cvxse::launched;
+using cvxse::over_grid;
 
 // (solve_lane2_kernel, the first phase of the lane-hybrid schedule: lane_kernel.hip, a translation unit of its own -- cvxb::launch_lane2)
 
@@ -107,7 +112,6 @@ __global__ void __launch_bounds__(64) assemble_subsets_kernel(int64_t batch, int
 struct Workspace { void *ptr = nullptr; size_t bytes = 0; int64_t cap = 0; size_t parked_bytes = 0; bool owned = true; };
 std::mutex g_ws_mutex;
 std::map<std::pair<int, void *>, Workspace> g_ws;
-thread_local char g_err[512] = "";
 thread_local int g_last_layout = 0; // the layout the last solve of this thread ran (cvxpnpl_last_layout)
 
 // One solve is two or three dependent launches that share the queue and the parked-iterate buffer of their (device, stream):
@@ -146,19 +150,17 @@ bool init_workspace(void *p, int64_t cap, void *stream)
 
 struct WsView { int32_t *count, *entries, *rq_count, *rq_entries; double *parked; };
 
-bool get_workspace(int64_t batch, int stride, void *stream, WsView &v)
+int get_workspace(int64_t batch, int stride, void *stream, WsView &v) // 0, or -2 with the message written
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { snprintf(g_err, sizeof(g_err), "cvxpnpl: hipGetDevice failed"); return false; }
+    if (hipGetDevice(&dev) != hipSuccess) return fail(-2, "cvxpnpl: hipGetDevice failed");
     std::lock_guard<std::mutex> lock(g_ws_mutex);
     Workspace &w = g_ws[std::make_pair(dev, stream)];
     const size_t need_parked = (size_t)batch * stride * sizeof(double);
     if (w.cap < batch || w.parked_bytes < need_parked) {
-        if (!w.owned) {
-            snprintf(g_err, sizeof(g_err), "cvxpnpl: the registered workspace holds %lld problems, the launch has %lld (cvxpnpl_workspace_bytes)",
-                     (long long)w.cap, (long long)batch);
-            return false;
-        }
+        if (!w.owned)
+            return fail(-2, "cvxpnpl: the registered workspace holds %lld problems, the launch has %lld (cvxpnpl_workspace_bytes)", (long long)w.cap,
+                        (long long)batch);
         const int64_t cap = w.cap > batch ? w.cap : batch;
         const size_t parked = w.parked_bytes > need_parked ? w.parked_bytes : need_parked;
         if (w.ptr) { (void)hipStreamSynchronize((hipStream_t)stream); (void)hipFree(w.ptr); }
@@ -167,8 +169,7 @@ bool get_workspace(int64_t batch, int stride, void *stream, WsView &v)
         if (hipMalloc(&w.ptr, bytes) != hipSuccess || !init_workspace(w.ptr, cap, stream)) {
             if (w.ptr) (void)hipFree(w.ptr);
             w.ptr = nullptr;
-            snprintf(g_err, sizeof(g_err), "cvxpnpl: workspace allocation failed (%zu bytes)", bytes);
-            return false;
+            return fail(-2, "cvxpnpl: workspace allocation failed (%zu bytes)", bytes);
         }
         w.bytes = bytes; w.cap = cap; w.parked_bytes = parked;
     }
@@ -177,13 +178,21 @@ bool get_workspace(int64_t batch, int stride, void *stream, WsView &v)
     v.rq_count = v.count + 16;
     v.rq_entries = (int32_t *)((char *)w.ptr + 256 + queue_entries_bytes(w.cap));
     v.parked = (double *)((char *)w.ptr + hybrid_queue_bytes(w.cap));
-    return true;
+    return 0;
+}
+
+// The variant dispatch: a launch of `rc` under the 16-equality ablation (cvx::VAR_RC), else of `full` (the reference's 22 equalities).
+// (`rc` first: the kernels come out in the device text in the order the callers name them, and tools/device_asm_diff.py compares text.)
+static_assert((int)CVXPNPL_VARIANT_FULL == (int)cvx::VAR_FULL && (int)CVXPNPL_VARIANT_RC == (int)cvx::VAR_RC, "the public variants are cvx::Variant");
+template <class... A>
+void launch_variant(int variant, void (*rc)(A...), void (*full)(A...), int64_t grid, int block, hipStream_t s, const A &...args)
+{
+    hipLaunchKernelGGL(variant == cvx::VAR_RC ? rc : full, dim3((unsigned)grid), dim3((unsigned)block), 0, s, args...);
 }
 
 void launch_wave(int64_t wgrid, hipStream_t s, const cvxw::WaveArgs &w, const cvx::Opts &o)
 {
-    if (o.variant == cvx::VAR_RC) hipLaunchKernelGGL(cvxw::solve_wave_kernel<cvx::VAR_RC>, dim3((unsigned)wgrid), dim3(64 * cvxw::WPB), 0, s, w, o);
-    else hipLaunchKernelGGL(cvxw::solve_wave_kernel<cvx::VAR_FULL>, dim3((unsigned)wgrid), dim3(64 * cvxw::WPB), 0, s, w, o);
+    launch_variant(o.variant, cvxw::solve_wave_kernel<cvx::VAR_RC>, cvxw::solve_wave_kernel<cvx::VAR_FULL>, wgrid, 64 * cvxw::WPB, s, w, o);
 }
 
 void launch_resume(int64_t rgrid, hipStream_t s, const cvxw::WaveArgs &w, const cvx::Opts &o, int32_t *count, int32_t *entries, const double *ws, bool full)
@@ -192,8 +201,7 @@ void launch_resume(int64_t rgrid, hipStream_t s, const cvxw::WaveArgs &w, const 
     ra.a = w; ra.o = o; ra.count_p = count; ra.entries = entries; ra.ws = ws;
     ra.ws_stride = full ? cvxw::RS_FULL : cvxw::RS_LANE; ra.ws_full = full ? 1 : 0;
     ra.count2 = nullptr; ra.entries2 = nullptr; ra.grid1 = 0;
-    if (o.variant == cvx::VAR_RC) hipLaunchKernelGGL(cvxw::resume_wave_kernel_rc, dim3((unsigned)rgrid), dim3(64), 0, s, ra);
-    else hipLaunchKernelGGL(cvxw::resume_wave_kernel, dim3((unsigned)rgrid), dim3(64), 0, s, ra);
+    launch_variant(o.variant, cvxw::resume_wave_kernel_rc, cvxw::resume_wave_kernel, rgrid, 64, s, ra);
 }
 
 // last launch of a solve with opts.rescue_from in force: the problems the other kernels gave up on (w.rq_count / w.rq_entries) and,
@@ -205,8 +213,7 @@ void launch_rescue(int64_t batch, hipStream_t s, const cvxw::WaveArgs &w, const 
     cvxw::ResumeArgs ra;
     ra.a = w; ra.o = o; ra.count_p = w.rq_count; ra.entries = w.rq_entries; ra.ws = ws; ra.ws_stride = cvxw::RS_FULL; ra.ws_full = 1;
     ra.count2 = count; ra.entries2 = entries; ra.grid1 = (int)rgrid;
-    if (o.variant == cvx::VAR_RC) hipLaunchKernelGGL(cvxw::rescue_wave_kernel_rc, dim3((unsigned)(count ? 2 * rgrid : rgrid)), dim3(64), 0, s, ra);
-    else hipLaunchKernelGGL(cvxw::rescue_wave_kernel, dim3((unsigned)(count ? 2 * rgrid : rgrid)), dim3(64), 0, s, ra);
+    launch_variant(o.variant, cvxw::rescue_wave_kernel_rc, cvxw::rescue_wave_kernel, count ? 2 * rgrid : rgrid, 64, s, ra);
 }
 
 // split interior-point path: the rescue queue through cvxi::ipm_quad_kernel (four solves per wavefront, ipm_quad.h) into the resume queue
@@ -220,14 +227,36 @@ void launch_ipm(int64_t batch, hipStream_t s, const cvxw::WaveArgs &w, const cvx
     ia.rq_count = w.rq_count; ia.rq_entries = w.rq_entries; ia.count = count; ia.entries = entries; ia.ws = w.rq_ws; ia.stride = w.rq_stride;
     ia.entries_cap = (int)(batch + cvxw::RESUME_GRID_MAX < 0x7fffffffLL ? batch + cvxw::RESUME_GRID_MAX : 0x7fffffffLL);
     ia.qs_in = nullptr; ia.z_out = nullptr; ia.s_out = nullptr; ia.gap_out = nullptr; ia.it_out = nullptr;
-    if (o.variant == cvx::VAR_RC) hipLaunchKernelGGL(cvxi::ipm_quad_kernel<cvx::VAR_RC>, dim3((unsigned)grid), dim3(64), 0, s, ia);
-    else hipLaunchKernelGGL(cvxi::ipm_quad_kernel<cvx::VAR_FULL>, dim3((unsigned)grid), dim3(64), 0, s, ia);
+    launch_variant(o.variant, cvxi::ipm_quad_kernel<cvx::VAR_RC>, cvxi::ipm_quad_kernel<cvx::VAR_FULL>, grid, 64, s, ia);
 }
 
-int set_err(const char *what, hipError_t e)
+// The argument block of a launch from an entry point's correspondence parameters, everything else null ...
+BatchArgs batch_inputs(int64_t batch, int32_t n_p, const double *p2, const double *p3, int32_t n_l, const double *l2, const double *l3, const double *K,
+                       int32_t K_per_problem)
 {
-    snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
-    return -2;
+    BatchArgs a;
+    memset(&a, 0, sizeof(a));
+    a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.K_per_problem = K_per_problem;
+    a.p2 = p2; a.p3 = p3; a.l2 = l2; a.l3 = l3; a.K = K;
+    return a;
+}
+
+// ... and the outputs of a solve
+void batch_outputs(BatchArgs &a, double *R, double *t, int32_t *status, int32_t *iters, double *cost, double *Z, int32_t *work)
+{
+    a.R = R; a.t = t; a.cost = cost; a.Z = Z; a.status = status; a.iters = iters; a.work = work;
+}
+
+// The wave kernels' view of an argument block: the same fields, then the queue of the interior-point path (filled by launch_solve).
+cvxw::WaveArgs wave_args(const BatchArgs &a)
+{
+    cvxw::WaveArgs w;
+    w.batch = a.batch; w.n_p = a.n_p; w.n_l = a.n_l; w.K_per_problem = a.K_per_problem;
+    w.p2 = a.p2; w.p3 = a.p3; w.l2 = a.l2; w.l3 = a.l3; w.K = a.K;
+    w.R = a.R; w.t = a.t; w.cost = a.cost; w.Z = a.Z; w.status = a.status; w.iters = a.iters; w.work = a.work;
+    w.Q45 = a.Q45; w.B27 = a.B27;
+    w.rq_count = nullptr; w.rq_entries = nullptr; w.rq_ws = nullptr; w.rq_stride = 0;
+    return w;
 }
 
 } // namespace
@@ -277,6 +306,13 @@ static void launch_quad(int64_t qgrid, hipStream_t s, cvxq::QuadArgs &qa, int de
     hipLaunchKernelGGL((cvxq::solve_quad_kernel<MODE, OCC, LPP, F64SW, VAR>), dim3((unsigned)qgrid), dim3(64), 0, s, qa);
 }
 
+// The order an entry point runs its checks in: its arguments (sizes, the pointers a launch would read or write, the scalars: one
+// condition, one message, -1), the zero-size no-op (0), what depends on the size (the limit of one launch, scratch: -1), then the launch
+// and its report (-2).  So an empty call with bad arguments is refused.  The entries that deviate: cvxpnpl_solve_batch,
+// cvxpnpl_solve_cost_batch and cvxpnpl_sample_minimal_sets take the no-op first (an empty call may pass anything);
+// cvxpnpl_assemble_subsets and cvxpnpl_ipm_batch have the limit of one launch among their arguments; cvxpnpl_select_best,
+// cvxpnpl_refit_update and cvxpnpl_calibration_copy have no empty call.  A null d_B of the two assemblies is refused without a message
+// (the text of an earlier failure stays), as is everything cvxpnpl_recover_multi_batch refuses (host_recover.cpp).
 extern "C" {
 
 void cvxpnpl_default_opts(cvxpnpl_opts_t *opts) { cvxplan::public_defaults(opts); }
@@ -288,10 +324,8 @@ int cvxpnpl_last_layout(void) { return g_last_layout; }
 static int check_args(int64_t batch, int32_t n_p, const double *p2, const double *p3, int32_t n_l, const double *l2,
                       const double *l3, const double *K)
 {
-    if (batch < 0 || n_p < 0 || n_l < 0 || (n_p == 0 && n_l == 0) || !K || (n_p > 0 && (!p2 || !p3)) || (n_l > 0 && (!l2 || !l3))) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl: bad arguments (batch=%lld n_p=%d n_l=%d)", (long long)batch, n_p, n_l);
-        return -1;
-    }
+    if (cvxse::bad_corr_block(batch, n_p, p2, p3, n_l, l2, l3, K) || (n_p == 0 && n_l == 0))
+        return fail(-1, "cvxpnpl: bad arguments (batch=%lld n_p=%d n_l=%d)", (long long)batch, n_p, n_l);
     return 0;
 }
 
@@ -301,25 +335,21 @@ static int launch_solve(const BatchArgs &a, const cvxpnpl_opts_t *opts, void *st
 {
     static constexpr cvxplan::Limits limits = {cvxw::RS_LANE, cvxw::RS_FULL, cvxw::RESUME_GRID_MAX, cvxi::IPMQ_GRID_MAX, cvxw::WPB};
     const int64_t batch = a.batch;
-    if (!a.R || !a.t || !a.status) { snprintf(g_err, sizeof(g_err), "cvxpnpl: R, t and status outputs are required"); return -1; }
-    if (!cvxplan::validate(opts, g_err, sizeof(g_err))) return -1;
+    if (!a.R || !a.t || !a.status) return fail(-1, "cvxpnpl: R, t and status outputs are required");
+    if (!cvxplan::validate(opts, cvxse::err_buf(), 512)) return -1;
     const cvxplan::SolvePlan p = cvxplan::plan_solve(batch, a.n_p, a.n_l, a.Q45 != nullptr, opts, limits);
-    if (p.too_large) { snprintf(g_err, sizeof(g_err), "cvxpnpl: batch too large for one launch"); return -1; }
+    if (p.too_large) return fail(-1, "cvxpnpl: batch too large for one launch");
     int cur_dev = 0;
-    if (hipGetDevice(&cur_dev) != hipSuccess) { snprintf(g_err, sizeof(g_err), "cvxpnpl: hipGetDevice failed"); return -2; }
+    if (hipGetDevice(&cur_dev) != hipSuccess) return fail(-2, "cvxpnpl: hipGetDevice failed");
     std::lock_guard<std::mutex> launch_lock(launch_mutex(cur_dev, stream)); // (see launch_mutex)
     hipStream_t s = (hipStream_t)stream;
     g_last_layout = p.last_layout;
     // ONE workspace view per solve: a second fetch with a larger stride may free and reallocate the buffer, and queue pointers taken
     // from the first would dangle
     WsView wv = {nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (p.needs_workspace && !get_workspace(batch, p.ws_stride, stream, wv)) return -2;
+    if (p.needs_workspace && get_workspace(batch, p.ws_stride, stream, wv)) return -2;
     const cvx::Opts &o = p.o;
-    cvxw::WaveArgs w;
-    w.batch = batch; w.n_p = a.n_p; w.n_l = a.n_l; w.K_per_problem = a.K_per_problem;
-    w.p2 = a.p2; w.p3 = a.p3; w.l2 = a.l2; w.l3 = a.l3; w.K = a.K;
-    w.R = a.R; w.t = a.t; w.cost = a.cost; w.Z = a.Z; w.status = a.status; w.iters = a.iters; w.work = a.work;
-    w.Q45 = a.Q45; w.B27 = a.B27;
+    cvxw::WaveArgs w = wave_args(a);
     w.rq_count = p.rescue ? wv.rq_count : nullptr; w.rq_entries = p.rescue ? wv.rq_entries : nullptr; // the interior-point path's queue
     w.rq_ws = p.split ? wv.parked : nullptr; w.rq_stride = p.split ? p.ws_stride : 0;
     cvxq::QuadArgs qa;
@@ -344,9 +374,7 @@ static int launch_solve(const BatchArgs &a, const cvxpnpl_opts_t *opts, void *st
         else if (f.two_queues) launch_rescue(batch, s, w, o, wv.count, wv.entries, wv.parked); // (both queues in one launch)
         else launch_rescue(batch, s, w, o);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err("solve kernel launch", e);
-    return 0;
+    return launched("solve kernel launch");
 }
 
 int cvxpnpl_solve_batch(int64_t batch, int32_t n_p, const double *d_pts_2d, const double *d_pts_3d, int32_t n_l,
@@ -356,11 +384,8 @@ int cvxpnpl_solve_batch(int64_t batch, int32_t n_p, const double *d_pts_2d, cons
 {
     if (batch == 0) return 0; /* empty batch: nothing to do (pointers may be NULL) */
     if (check_args(batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K)) return -1;
-    BatchArgs a;
-    a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.K_per_problem = K_per_problem;
-    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.K = d_K;
-    a.R = d_R; a.t = d_t; a.cost = d_cost; a.Z = d_Z; a.status = d_status; a.iters = d_iters; a.work = d_work;
-    a.Q45 = nullptr; a.B27 = nullptr;
+    BatchArgs a = batch_inputs(batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K, K_per_problem);
+    batch_outputs(a, d_R, d_t, d_status, d_iters, d_cost, d_Z, d_work);
     return launch_solve(a, opts, stream);
 }
 
@@ -368,12 +393,10 @@ int cvxpnpl_solve_cost_batch(int64_t batch, const double *d_Q45, const double *d
                              double *d_t, int32_t *d_status, int32_t *d_iters, double *d_cost, double *d_Z, int32_t *d_work, void *stream)
 {
     if (batch == 0) return 0;
-    if (batch < 0 || !d_Q45 || !d_B27) { snprintf(g_err, sizeof(g_err), "cvxpnpl_solve_cost_batch: bad arguments (batch=%lld)", (long long)batch); return -1; }
-    BatchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.batch = batch;
-    a.R = d_R; a.t = d_t; a.cost = d_cost; a.Z = d_Z; a.status = d_status; a.iters = d_iters; a.work = d_work;
+    if (batch < 0 || !d_Q45 || !d_B27) return fail(-1, "cvxpnpl_solve_cost_batch: bad arguments (batch=%lld)", (long long)batch);
+    BatchArgs a = batch_inputs(batch, 0, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0); // (no correspondences: the cost itself)
     a.Q45 = d_Q45; a.B27 = d_B27;
+    batch_outputs(a, d_R, d_t, d_status, d_iters, d_cost, d_Z, d_work);
     return launch_solve(a, opts, stream);
 }
 
@@ -383,29 +406,21 @@ int cvxpnpl_assemble_batch(int64_t batch, int32_t n_p, const double *d_pts_2d, c
 {
     if (check_args(batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K) || !d_B) return -1;
     if (batch == 0) return 0;
-    BatchArgs a;
-    memset(&a, 0, sizeof(a));
-    a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.K_per_problem = K_per_problem;
-    a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.K = d_K;
+    const BatchArgs a = batch_inputs(batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K, K_per_problem);
     const int block = 64;
     hipLaunchKernelGGL(assemble_kernel, dim3((unsigned)((batch + block - 1) / block)), dim3(block), 0, (hipStream_t)stream, a, d_B, d_Q45);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err("assemble_kernel launch", e);
-    return 0;
+    return launched("assemble_kernel launch");
 }
 
 int cvxpnpl_assemble_subsets(int64_t batch, int32_t n_corr, const double *d_scene_2d, const double *d_scene_3d, const uint8_t *d_mask, const double *d_K,
                              double *d_B, double *d_Q45, int32_t *d_count, void *stream)
 {
-    if (batch < 0 || n_corr < 1 || (batch + 63) / 64 > 0x7fffffffLL || (batch > 0 && (!d_scene_2d || !d_scene_3d || !d_mask || !d_K || !d_B || !d_Q45))) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_assemble_subsets: bad arguments");
-        return -1;
-    }
+    if (batch < 0 || n_corr < 1 || (batch + 63) / 64 > cvxse::GRID_MAX || (batch > 0 && (!d_scene_2d || !d_scene_3d || !d_mask || !d_K || !d_B || !d_Q45)))
+        return fail(-1, "cvxpnpl_assemble_subsets: bad arguments");
     if (batch == 0) return 0;
     hipLaunchKernelGGL(assemble_subsets_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, batch, (int)n_corr, d_scene_2d, d_scene_3d,
                        d_mask, d_K, d_B, d_Q45, d_count);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("assemble_subsets_kernel launch", e);
+    return launched("assemble_subsets_kernel launch");
 }
 
 size_t cvxpnpl_assemble_large_scratch_bytes(int64_t batch, int32_t n_p, int32_t n_l)
@@ -420,12 +435,10 @@ int cvxpnpl_assemble_large_batch(int64_t batch, int32_t n_p, const double *d_pts
 {
     if (check_args(batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K) || !d_B) return -1;
     if (batch == 0) return 0;
-    if (batch > 65535) { snprintf(g_err, sizeof(g_err), "cvxpnpl_assemble_large_batch: at most 65535 problems per call (got %lld)", (long long)batch); return -1; }
+    if (batch > 65535) return fail(-1, "cvxpnpl_assemble_large_batch: at most 65535 problems per call (got %lld)", (long long)batch);
     const size_t need = cvxpnpl_assemble_large_scratch_bytes(batch, n_p, n_l);
-    if (!d_scratch || scratch_bytes < need) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_assemble_large_batch: scratch of %zu bytes needed (cvxpnpl_assemble_large_scratch_bytes), got %zu", need, scratch_bytes);
-        return -1;
-    }
+    if (!d_scratch || scratch_bytes < need)
+        return fail(-1, "cvxpnpl_assemble_large_batch: scratch of %zu bytes needed (cvxpnpl_assemble_large_scratch_bytes), got %zu", need, scratch_bytes);
     cvxa::AsmArgs a;
     a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.K_per_problem = K_per_problem;
     a.nblk = cvxa::asm_blocks((int64_t)n_p + 2 * (int64_t)n_l, batch);
@@ -438,64 +451,53 @@ int cvxpnpl_assemble_large_batch(int64_t batch, int32_t n_p, const double *d_pts
         hipLaunchKernelGGL(cvxa::assemble_large_kernel<cvxa::ASM_TPB_NARROW>, dim3((unsigned)a.nblk, (unsigned)batch), dim3(cvxa::ASM_TPB_NARROW), 0, (hipStream_t)stream, a);
     if (a.nblk > 1) // several workgroups per problem: their partial sums are added in a fixed order by a second kernel
         hipLaunchKernelGGL(cvxa::assemble_finish_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, a, d_B, d_Q45);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err("assemble_large_kernel launch", e);
-    return 0;
+    return launched("assemble_large_kernel launch");
 }
 
 int cvxpnpl_synth_batch(int64_t batch, int32_t n_p, int32_t n_l, double sigma, uint64_t seed, const double *d_K, double *d_pts_2d,
                         double *d_pts_3d, double *d_line_2d, double *d_line_3d, double *d_R_gt, double *d_t_gt, void *stream)
 {
-    if (batch < 0 || n_p < 0 || n_l < 0 || !d_K || !(sigma >= 0.0) || (n_p > 0 && (!d_pts_2d || !d_pts_3d)) || (n_l > 0 && (!d_line_2d || !d_line_3d))) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_synth_batch: bad arguments");
-        return -1;
-    }
+    if (cvxse::bad_corr_block(batch, n_p, d_pts_2d, d_pts_3d, n_l, d_line_2d, d_line_3d, d_K) || !(sigma >= 0.0)) return fail(-1, "cvxpnpl_synth_batch: bad arguments");
     if (batch == 0) return 0;
     cvxg::SynthArgs a;
     a.batch = batch; a.n_p = n_p; a.n_l = n_l; a.sigma = sigma; a.length = 0.6 /* synth.py:55 */; a.seed = seed; a.K = d_K;
     a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.l2 = d_line_2d; a.l3 = d_line_3d; a.R_gt = d_R_gt; a.t_gt = d_t_gt;
     const int64_t nrec = (int64_t)n_p + 2 * (int64_t)n_l, n = batch * (nrec > 0 ? nrec : 1), grid = (n + 255) / 256;
-    if (grid > 0x7fffffffLL) { snprintf(g_err, sizeof(g_err), "cvxpnpl_synth_batch: too many records for one launch"); return -1; }
+    if (over_grid(grid, "cvxpnpl_synth_batch: too many records for one launch")) return -1;
     hipLaunchKernelGGL(cvxg::synth_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("synth_kernel launch", e);
+    return launched("synth_kernel launch");
 }
 
 int cvxpnpl_pose_errors(int64_t batch, const double *d_R_gt, const double *d_t_gt, const double *d_R, const double *d_t, double *d_ang_deg,
                         double *d_trans, void *stream)
 {
-    if (batch < 0 || !d_R_gt || !d_t_gt || !d_R || !d_t || !d_ang_deg || !d_trans) { snprintf(g_err, sizeof(g_err), "cvxpnpl_pose_errors: bad arguments"); return -1; }
+    if (batch < 0 || !d_R_gt || !d_t_gt || !d_R || !d_t || !d_ang_deg || !d_trans) return fail(-1, "cvxpnpl_pose_errors: bad arguments");
     if (batch == 0) return 0;
     hipLaunchKernelGGL(cvxg::pose_error_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, batch, d_R_gt, d_t_gt, d_R, d_t,
                        d_ang_deg, d_trans);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("pose_error_kernel launch", e);
+    return launched("pose_error_kernel launch");
 }
 
 int cvxpnpl_disambiguate(int64_t batch, const double *d_R_all, const double *d_t_all, const int32_t *d_n_poses, const double *d_K,
                          const double *d_R_gt, const double *d_t_gt, const double *d_support, int32_t n_support, double *d_R, double *d_t,
                          int32_t *d_index, void *stream)
 {
-    if (batch < 0 || !d_R_all || !d_t_all || !d_n_poses || !d_K || !d_R_gt || !d_t_gt || (n_support > 0 && !d_support) || n_support < 0 || !d_R || !d_t || !d_index) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_disambiguate: bad arguments");
-        return -1;
-    }
+    if (batch < 0 || !d_R_all || !d_t_all || !d_n_poses || !d_K || !d_R_gt || !d_t_gt || (n_support > 0 && !d_support) || n_support < 0 || !d_R || !d_t || !d_index)
+        return fail(-1, "cvxpnpl_disambiguate: bad arguments");
     if (batch == 0) return 0;
     hipLaunchKernelGGL(cvxg::disambiguate_kernel, dim3((unsigned)((batch + 255) / 256)), dim3(256), 0, (hipStream_t)stream, batch, d_R_all, d_t_all,
                        d_n_poses, d_K, d_R_gt, d_t_gt, d_support, n_support, d_R, d_t, d_index);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("disambiguate_kernel launch", e);
+    return launched("disambiguate_kernel launch");
 }
 
 int cvxpnpl_recover_multi_device(int64_t batch, const int32_t *d_status, const double *d_Z55, const double *d_B27, const double *d_Q45,
                                  double *d_R_out, double *d_t_out, int32_t *d_n_poses, void *stream)
 {
-    if (batch < 0 || !d_Z55 || !d_B27 || !d_R_out || !d_t_out || !d_n_poses) { snprintf(g_err, sizeof(g_err), "cvxpnpl_recover_multi_device: bad arguments"); return -1; }
+    if (batch < 0 || !d_Z55 || !d_B27 || !d_R_out || !d_t_out || !d_n_poses) return fail(-1, "cvxpnpl_recover_multi_device: bad arguments");
     if (batch == 0) return 0;
     hipLaunchKernelGGL(cvxr::recover_multi_kernel, dim3((unsigned)((batch + 63) / 64)), dim3(64), 0, (hipStream_t)stream, batch, d_status, d_Z55, d_B27,
                        d_Q45, d_R_out, d_t_out, d_n_poses);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("recover_multi_kernel launch", e);
+    return launched("recover_multi_kernel launch");
 }
 
 // Ordering between two streams of one device without a HIP event on the producing stream: the producer enqueues a one-lane kernel
@@ -535,19 +537,17 @@ __global__ void stream_wait_value_kernel(unsigned long long *flag, unsigned long
 
 int cvxpnpl_stream_write_value(uint64_t *d_flag, uint64_t value, void *stream)
 {
-    if (!d_flag) { snprintf(g_err, sizeof(g_err), "cvxpnpl_stream_write_value: null flag"); return -1; }
+    if (!d_flag) return fail(-1, "cvxpnpl_stream_write_value: null flag");
     hipLaunchKernelGGL(stream_write_value_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long *)d_flag, (unsigned long long)value);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("stream_write_value_kernel launch", e);
+    return launched("stream_write_value_kernel launch");
 }
 
 static int launch_wait(uint64_t *d_flag, uint64_t value, uint64_t max_polls, int closed, void *stream)
 {
-    if (!d_flag) { snprintf(g_err, sizeof(g_err), "cvxpnpl_stream_wait_value: null flag"); return -1; }
+    if (!d_flag) return fail(-1, "cvxpnpl_stream_wait_value: null flag");
     hipLaunchKernelGGL(stream_wait_value_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, (unsigned long long *)d_flag, (unsigned long long)value,
                        (unsigned long long)max_polls, closed, 1ull << 25);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("stream_wait_value_kernel launch", e);
+    return launched("stream_wait_value_kernel launch");
 }
 
 int cvxpnpl_stream_wait_value_bounded(uint64_t *d_flag, uint64_t value, uint64_t max_polls, void *stream) { return launch_wait(d_flag, value, max_polls, 0, stream); }
@@ -568,13 +568,13 @@ static hipStream_t ack_stream()
 
 int cvxpnpl_stream_wait_gave_up(uint64_t *d_flag, int32_t clear, void *stream)
 {
-    if (!d_flag) { snprintf(g_err, sizeof(g_err), "cvxpnpl_stream_wait_gave_up: null flag"); return -1; }
+    if (!d_flag) return fail(-1, "cvxpnpl_stream_wait_gave_up: null flag");
     hipStream_t as = ack_stream();
-    if (!as) { snprintf(g_err, sizeof(g_err), "cvxpnpl_stream_wait_gave_up: no stream for the acknowledgement"); return -2; }
+    if (!as) return fail(-2, "cvxpnpl_stream_wait_gave_up: no stream for the acknowledgement");
     for (;;) {
         // (the state of `stream` is sampled BEFORE the word: when the stream was already idle no wait of it can set the word afterwards)
         const hipError_t q = hipStreamQuery((hipStream_t)stream);
-        if (q != hipSuccess && q != hipErrorNotReady) return set_err("cvxpnpl_stream_wait_gave_up (stream)", q);
+        if (q != hipSuccess && q != hipErrorNotReady) return hip_error("cvxpnpl_stream_wait_gave_up (stream)", q);
         unsigned long long w = 0;
         hipError_t e = hipMemcpyAsync(&w, d_flag + 1, sizeof(w), hipMemcpyDeviceToHost, as);
         if (e == hipSuccess) e = hipStreamSynchronize(as);
@@ -582,7 +582,7 @@ int cvxpnpl_stream_wait_gave_up(uint64_t *d_flag, int32_t clear, void *stream)
             e = hipMemsetAsync(d_flag + 1, 0, sizeof(w), as); // releases a closed wait that is holding `stream`
             if (e == hipSuccess) e = hipStreamSynchronize(as);
         }
-        if (e != hipSuccess) return set_err("cvxpnpl_stream_wait_gave_up", e);
+        if (e != hipSuccess) return hip_error("cvxpnpl_stream_wait_gave_up", e);
         if (w != 0) return 1;
         if (q == hipSuccess) return 0; // everything the waits ordered is complete, and none gave up
         usleep(50);
@@ -591,14 +591,12 @@ int cvxpnpl_stream_wait_gave_up(uint64_t *d_flag, int32_t clear, void *stream)
 
 int cvxpnpl_pack_results(int64_t batch, const double *d_R, const double *d_t, const int32_t *d_status, double *d_packed, void *stream)
 {
-    if (batch < 0 || !d_R || !d_t || !d_status || !d_packed) { snprintf(g_err, sizeof(g_err), "cvxpnpl_pack_results: bad arguments"); return -1; }
+    if (batch < 0 || !d_R || !d_t || !d_status || !d_packed) return fail(-1, "cvxpnpl_pack_results: bad arguments");
     if (batch == 0) return 0;
     const int64_t n = batch * 13, grid = (n + 255) / 256;
-    if (grid > 0x7fffffffLL) { snprintf(g_err, sizeof(g_err), "cvxpnpl_pack_results: batch too large for one launch"); return -1; }
+    if (over_grid(grid, "cvxpnpl_pack_results: batch too large for one launch")) return -1;
     hipLaunchKernelGGL(pack_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, batch, d_R, d_t, d_status, d_packed);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err("pack_kernel launch", e);
-    return 0;
+    return launched("pack_kernel launch");
 }
 
 int cvxpnpl_select_best(int64_t n_hyp, const int32_t *d_count, const double *d_R, const double *d_t, const int32_t *d_status, const double *d_K,
@@ -606,14 +604,11 @@ int cvxpnpl_select_best(int64_t n_hyp, const int32_t *d_count, const double *d_R
                         int32_t *d_head, uint8_t *d_mask, void *stream)
 {
     if (n_hyp < 1 || n_hyp > 0x7fffffffLL || n_corr < 0 || !d_count || !d_R || !d_t || !d_status || !d_K || !d_out_R || !d_out_t || !d_head ||
-        (n_corr > 0 && (!d_pts_2d || !d_pts_3d || !d_mask)) || !(thresh_px > 0.0)) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_select_best: bad arguments");
-        return -1;
-    }
+        (n_corr > 0 && (!d_pts_2d || !d_pts_3d || !d_mask)) || !(thresh_px > 0.0))
+        return fail(-1, "cvxpnpl_select_best: bad arguments");
     cvxs::SelectArgs a{n_hyp, d_count, d_R, d_t, d_status, d_K, n_corr, d_pts_2d, d_pts_3d, thresh_px, d_out_R, d_out_t, d_head, d_mask};
     hipLaunchKernelGGL(cvxs::select_best_kernel, dim3(1), dim3(cvxs::SELECT_BLOCK), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("select_best_kernel launch", e);
+    return launched("select_best_kernel launch");
 }
 
 int cvxpnpl_refit_update(const double *d_fit_R, const double *d_fit_t, const int32_t *d_fit_status, const int32_t *d_fit_count, const double *d_K,
@@ -621,51 +616,41 @@ int cvxpnpl_refit_update(const double *d_fit_R, const double *d_fit_t, const int
                          uint8_t *d_mask, void *stream)
 {
     if (n_corr < 0 || !d_fit_R || !d_fit_t || !d_fit_status || !d_fit_count || !d_K || !d_R || !d_t || !d_head ||
-        (n_corr > 0 && (!d_pts_2d || !d_pts_3d || !d_mask)) || !(thresh_px > 0.0)) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_refit_update: bad arguments");
-        return -1;
-    }
+        (n_corr > 0 && (!d_pts_2d || !d_pts_3d || !d_mask)) || !(thresh_px > 0.0))
+        return fail(-1, "cvxpnpl_refit_update: bad arguments");
     cvxs::RefitArgs a{d_fit_R, d_fit_t, d_fit_status, d_fit_count, d_K, n_corr, d_pts_2d, d_pts_3d, thresh_px, d_R, d_t, d_head, d_mask};
     hipLaunchKernelGGL(cvxs::refit_update_kernel, dim3(1), dim3(cvxs::SELECT_BLOCK), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("refit_update_kernel launch", e);
+    return launched("refit_update_kernel launch");
 }
 
 int cvxpnpl_score_hypotheses(int64_t n_hyp, const double *d_R, const double *d_t, const int32_t *d_status, uint32_t usable_mask,
                              const double *d_K, int32_t n_corr, const double *d_pts_2d, const double *d_pts_3d, double thresh_px,
                              int32_t *d_count, uint8_t *d_mask, void *stream)
 {
-    if (n_hyp < 0 || n_corr < 0 || !d_R || !d_t || !d_K || !d_count || (n_corr > 0 && (!d_pts_2d || !d_pts_3d)) || !(thresh_px > 0.0)) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_score_hypotheses: bad arguments");
-        return -1;
-    }
+    if (n_hyp < 0 || n_corr < 0 || !d_R || !d_t || !d_K || !d_count || (n_corr > 0 && (!d_pts_2d || !d_pts_3d)) || !(thresh_px > 0.0))
+        return fail(-1, "cvxpnpl_score_hypotheses: bad arguments");
     if (n_hyp == 0) return 0;
     const int64_t grid = (n_hyp + cvxs::SCORE_BLOCK - 1) / cvxs::SCORE_BLOCK;
-    if (grid > 0x7fffffffLL) { snprintf(g_err, sizeof(g_err), "cvxpnpl_score_hypotheses: too many hypotheses for one launch"); return -1; }
+    if (over_grid(grid, "cvxpnpl_score_hypotheses: too many hypotheses for one launch")) return -1;
     cvxs::ScoreArgs a;
     a.n_hyp = n_hyp; a.R = d_R; a.t = d_t; a.status = d_status; a.usable_mask = usable_mask; a.K = d_K;
     a.n_corr = n_corr; a.p2 = d_pts_2d; a.p3 = d_pts_3d; a.thresh = thresh_px; a.count = d_count; a.mask = d_mask;
     hipLaunchKernelGGL(cvxs::score_kernel, dim3((unsigned)grid), dim3(cvxs::SCORE_BLOCK), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return set_err("score_kernel launch", e);
-    return 0;
+    return launched("score_kernel launch");
 }
 
 int cvxpnpl_sample_minimal_sets(int64_t n_hyp, int32_t n_corr, const double *d_scene_2d, const double *d_scene_3d, int32_t k, uint64_t seed,
                                 int32_t *d_idx, double *d_pts_2d, double *d_pts_3d, void *stream)
 {
     if (n_hyp == 0) return 0; /* a no-op, as the header says: the (empty) outputs may be NULL */
-    if (n_hyp < 0 || k < 1 || k > cvxs::SAMPLE_KMAX || n_corr < k || !d_scene_2d || !d_scene_3d || !d_pts_2d || !d_pts_3d) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_sample_minimal_sets: bad arguments (n_hyp=%lld n_corr=%d k=%d)", (long long)n_hyp, n_corr, k);
-        return -1;
-    }
+    if (n_hyp < 0 || k < 1 || k > cvxs::SAMPLE_KMAX || n_corr < k || !d_scene_2d || !d_scene_3d || !d_pts_2d || !d_pts_3d)
+        return fail(-1, "cvxpnpl_sample_minimal_sets: bad arguments (n_hyp=%lld n_corr=%d k=%d)", (long long)n_hyp, n_corr, k);
     const int64_t grid = (n_hyp + 255) / 256;
-    if (grid > 0x7fffffffLL) { snprintf(g_err, sizeof(g_err), "cvxpnpl_sample_minimal_sets: too many hypotheses for one launch"); return -1; }
+    if (over_grid(grid, "cvxpnpl_sample_minimal_sets: too many hypotheses for one launch")) return -1;
     cvxs::SampleArgs a;
     a.n_hyp = n_hyp; a.n_corr = n_corr; a.k = k; a.seed = seed; a.s2 = d_scene_2d; a.s3 = d_scene_3d; a.idx = d_idx; a.p2 = d_pts_2d; a.p3 = d_pts_3d;
     hipLaunchKernelGGL(cvxs::sample_sets_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("sample_sets_kernel launch", e);
+    return launched("sample_sets_kernel launch");
 }
 
 size_t cvxpnpl_workspace_bytes(int64_t max_batch) { return max_batch > 0 ? hybrid_ws_bytes(max_batch) : 0; }
@@ -673,7 +658,7 @@ size_t cvxpnpl_workspace_bytes(int64_t max_batch) { return max_batch > 0 ? hybri
 int cvxpnpl_set_workspace(void *d_workspace, size_t bytes, void *stream)
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { snprintf(g_err, sizeof(g_err), "cvxpnpl: hipGetDevice failed"); return -2; }
+    if (hipGetDevice(&dev) != hipSuccess) return fail(-2, "cvxpnpl: hipGetDevice failed");
     std::lock_guard<std::mutex> launch_lock(launch_mutex(dev, stream)); // no solve of this stream is between its launches
     std::lock_guard<std::mutex> lock(g_ws_mutex);
     Workspace &w = g_ws[std::make_pair(dev, stream)];
@@ -681,8 +666,8 @@ int cvxpnpl_set_workspace(void *d_workspace, size_t bytes, void *stream)
     w = Workspace();
     if (!d_workspace) return 0; // back to the library's own allocation
     const int64_t cap = hybrid_capacity(bytes);
-    if (cap <= 0) { snprintf(g_err, sizeof(g_err), "cvxpnpl_set_workspace: %zu bytes hold no problem (cvxpnpl_workspace_bytes)", bytes); g_ws.erase(std::make_pair(dev, stream)); return -1; }
-    if (!init_workspace(d_workspace, cap, stream)) { g_ws.erase(std::make_pair(dev, stream)); return set_err("cvxpnpl_set_workspace", hipGetLastError()); }
+    if (cap <= 0) { g_ws.erase(std::make_pair(dev, stream)); return fail(-1, "cvxpnpl_set_workspace: %zu bytes hold no problem (cvxpnpl_workspace_bytes)", bytes); }
+    if (!init_workspace(d_workspace, cap, stream)) { g_ws.erase(std::make_pair(dev, stream)); return hip_error("cvxpnpl_set_workspace", hipGetLastError()); }
     w.ptr = d_workspace; w.bytes = bytes; w.cap = cap; w.parked_bytes = bytes - hybrid_queue_bytes(cap); w.owned = false;
     return 0;
 }
@@ -690,7 +675,7 @@ int cvxpnpl_set_workspace(void *d_workspace, size_t bytes, void *stream)
 int cvxpnpl_release_workspace(void *stream, int32_t all_streams)
 {
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) { snprintf(g_err, sizeof(g_err), "cvxpnpl: hipGetDevice failed"); return -2; }
+    if (hipGetDevice(&dev) != hipSuccess) return fail(-2, "cvxpnpl: hipGetDevice failed");
     std::vector<void *> streams;
     {
         std::lock_guard<std::mutex> lock(g_ws_mutex);
@@ -710,34 +695,26 @@ int cvxpnpl_release_workspace(void *stream, int32_t all_streams)
 
 int cvxpnpl_ipm_batch(int64_t batch, const double *d_Qs55, int32_t variant, double *d_Z100, double *d_S100, double *d_gap, int32_t *d_iters, void *stream)
 {
-    if (batch < 0 || !d_Qs55 || !d_Z100 || !d_S100 || !d_gap || !d_iters || (variant != CVXPNPL_VARIANT_FULL && variant != CVXPNPL_VARIANT_RC) || (batch + 3) / 4 > 0x7fffffffLL) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_ipm_batch: bad arguments");
-        return -1;
-    }
+    if (batch < 0 || !d_Qs55 || !d_Z100 || !d_S100 || !d_gap || !d_iters || (variant != CVXPNPL_VARIANT_FULL && variant != CVXPNPL_VARIANT_RC) || (batch + 3) / 4 > cvxse::GRID_MAX)
+        return fail(-1, "cvxpnpl_ipm_batch: bad arguments");
     if (batch == 0) return 0;
     cvxi::IpmQuadArgs ia;
     memset(&ia, 0, sizeof(ia));
     ia.batch = batch; ia.rho = 1.0; ia.rho_tail = 1.0;
     ia.qs_in = d_Qs55; ia.z_out = d_Z100; ia.s_out = d_S100; ia.gap_out = d_gap; ia.it_out = d_iters;
-    const unsigned grid = (unsigned)((batch + 3) / 4);
-    if (variant == CVXPNPL_VARIANT_RC) hipLaunchKernelGGL(cvxi::ipm_quad_kernel<cvx::VAR_RC>, dim3(grid), dim3(64), 0, (hipStream_t)stream, ia);
-    else hipLaunchKernelGGL(cvxi::ipm_quad_kernel<cvx::VAR_FULL>, dim3(grid), dim3(64), 0, (hipStream_t)stream, ia);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("ipm_quad_kernel launch", e);
+    launch_variant(variant, cvxi::ipm_quad_kernel<cvx::VAR_RC>, cvxi::ipm_quad_kernel<cvx::VAR_FULL>, (batch + 3) / 4, 64, (hipStream_t)stream, ia); // (CVXPNPL_VARIANT_* are cvx::VAR_*)
+    return launched("ipm_quad_kernel launch");
 }
 
 int cvxpnpl_calibration_copy(const void *d_src, void *d_dst, int64_t nbytes, int32_t bytes_per_lane, void *stream)
 {
-    if (!d_src || !d_dst || nbytes <= 0 || (bytes_per_lane != 4 && bytes_per_lane != 8 && bytes_per_lane != 16) || nbytes % 16) {
-        snprintf(g_err, sizeof(g_err), "cvxpnpl_calibration_copy: bad arguments");
-        return -1;
-    }
+    if (!d_src || !d_dst || nbytes <= 0 || (bytes_per_lane != 4 && bytes_per_lane != 8 && bytes_per_lane != 16) || nbytes % 16)
+        return fail(-1, "cvxpnpl_calibration_copy: bad arguments");
     const dim3 grid(4096), block(256);
     if (bytes_per_lane == 4) hipLaunchKernelGGL(cvxd::calibration_copy_kernel<4>, grid, block, 0, (hipStream_t)stream, (const char *)d_src, (char *)d_dst, nbytes);
     if (bytes_per_lane == 8) hipLaunchKernelGGL(cvxd::calibration_copy_kernel<8>, grid, block, 0, (hipStream_t)stream, (const char *)d_src, (char *)d_dst, nbytes);
     if (bytes_per_lane == 16) hipLaunchKernelGGL(cvxd::calibration_copy_kernel<16>, grid, block, 0, (hipStream_t)stream, (const char *)d_src, (char *)d_dst, nbytes);
-    hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : set_err("calibration_copy_kernel launch", e);
+    return launched("calibration_copy_kernel launch");
 }
 
 void *cvxpnpl_event_create(void)
@@ -749,18 +726,18 @@ void *cvxpnpl_event_create(void)
 int cvxpnpl_event_record(void *event, void *stream)
 {
     hipError_t e = hipEventRecord((hipEvent_t)event, (hipStream_t)stream);
-    return e == hipSuccess ? 0 : set_err("hipEventRecord", e);
+    return e == hipSuccess ? 0 : hip_error("hipEventRecord", e);
 }
 int cvxpnpl_event_elapsed_ms(void *start, void *stop, float *ms)
 {
     hipError_t e = hipEventSynchronize((hipEvent_t)stop);
-    if (e != hipSuccess) return set_err("hipEventSynchronize", e);
+    if (e != hipSuccess) return hip_error("hipEventSynchronize", e);
     e = hipEventElapsedTime(ms, (hipEvent_t)start, (hipEvent_t)stop);
-    return e == hipSuccess ? 0 : set_err("hipEventElapsedTime", e);
+    return e == hipSuccess ? 0 : hip_error("hipEventElapsedTime", e);
 }
 void cvxpnpl_event_destroy(void *event) { if (event) hipEventDestroy((hipEvent_t)event); }
 
-const char *cvxpnpl_last_error(void) { return g_err; }
+const char *cvxpnpl_last_error(void) { return cvxse::err_buf(); }
 const char *cvxpnpl_version(void) { return "cvxpnpl_amd 0.1.0 (gfx950)"; }
 int cvxpnpl_device_count(void)
 {

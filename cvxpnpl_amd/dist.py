@@ -105,13 +105,12 @@ def pack_results(R: torch.Tensor, t: torch.Tensor, status: torch.Tensor) -> torc
         import ctypes as C
 
         from . import _lib
+        from .api import _call, _stream
 
         Rc, tc, sc = R.contiguous(), t.contiguous(), status.to(torch.int32).contiguous()
         with torch.cuda.device(R.device):
-            rc = _lib.lib().cvxpnpl_pack_results(n, C.c_void_p(Rc.data_ptr()), C.c_void_p(tc.data_ptr()), C.c_void_p(sc.data_ptr()),
-                                                 C.c_void_p(out.data_ptr()), C.c_void_p(torch.cuda.current_stream(R.device).cuda_stream))
-        if rc != 0:
-            raise RuntimeError(f"cvxpnpl_pack_results failed ({rc}): {_lib.last_error()}")
+            _call(_lib.lib(), "cvxpnpl_pack_results", n, C.c_void_p(Rc.data_ptr()), C.c_void_p(tc.data_ptr()), C.c_void_p(sc.data_ptr()),
+                  C.c_void_p(out.data_ptr()), _stream(R.device))
         return out
     if n == 0:
         return out

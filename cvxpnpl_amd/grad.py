@@ -17,7 +17,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .api import _as_dev, _ptr, _require_gpu, pnpl_batch
+from .api import _as_dev, _call, _ptr, _require_gpu, _stream, pnpl_batch
 
 __all__ = ["pose_vjp", "pose_vjp_host", "pnpl_batch_diff", "pnp_batch_diff", "pnl_batch_diff", "ADMIT_CERTIFIED", "ADMIT_RANK1"]
 
@@ -62,11 +62,9 @@ def pose_vjp(R, t, status, grad_R=None, grad_t=None, pts_2d=None, line_2d=None, 
     vst = torch.empty(batch, device=device, dtype=torch.int32)
     info = torch.empty((batch, 2), **f64) if want_info else None
     with torch.cuda.device(device):
-        rc = L.cvxpnpl_pose_vjp_batch(batch, n_p, _ptr(p2), _ptr(p3), n_l, _ptr(l2), _ptr(l3), _ptr(Kd), per, _ptr(Rd), _ptr(td), _ptr(st),
-                                      int(admit_mask), _ptr(gR), _ptr(gt), _ptr(out["pts_2d"]), _ptr(out["pts_3d"]), _ptr(out["line_2d"]),
-                                      _ptr(out["line_3d"]), _ptr(vst), _ptr(info), C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_pose_vjp_batch failed ({rc}): {_lib.grad_lib().cvxpnpl_grad_last_error().decode()}")
+        _call(L, "cvxpnpl_pose_vjp_batch", batch, n_p, _ptr(p2), _ptr(p3), n_l, _ptr(l2), _ptr(l3), _ptr(Kd), per, _ptr(Rd), _ptr(td), _ptr(st),
+              int(admit_mask), _ptr(gR), _ptr(gt), _ptr(out["pts_2d"]), _ptr(out["pts_3d"]), _ptr(out["line_2d"]), _ptr(out["line_3d"]), _ptr(vst),
+              _ptr(info), _stream(device), last_error="cvxpnpl_grad_last_error")
     out["vjp_status"] = vst
     if want_info:
         out["info"] = info

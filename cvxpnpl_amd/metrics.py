@@ -83,17 +83,16 @@ def pose_errors_device(R_gt, t_gt, R, t):
     import torch
 
     from . import _lib
+    from .api import _call, _device_of, _stream
 
-    dev = R.device if isinstance(R, torch.Tensor) and R.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(None, R)
     Rg, tg, Rd, td = (_dev_f64(x, dev) for x in (R_gt, t_gt, R, t))
     B = Rd.shape[0]
     ang = torch.empty((B,), dtype=torch.float64, device=dev)
     trans = torch.empty((B,), dtype=torch.float64, device=dev)
     p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
     with torch.cuda.device(dev):
-        rc = _lib.lib().cvxpnpl_pose_errors(B, p(Rg), p(tg), p(Rd), p(td), p(ang), p(trans), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_pose_errors failed ({rc}): {_lib.last_error()}")
+        _call(_lib.lib(), "cvxpnpl_pose_errors", B, p(Rg), p(tg), p(Rd), p(td), p(ang), p(trans), _stream(dev))
     return ang, trans
 
 
@@ -105,8 +104,9 @@ def disambiguate_device(R_all, t_all, n_poses, K, R_gt, t_gt, n_support: int = 2
     import torch
 
     from . import _lib
+    from .api import _call, _device_of, _stream
 
-    dev = R_gt.device if isinstance(R_gt, torch.Tensor) and R_gt.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(None, R_gt)
     Ra, ta, Kd, Rg, tg = (_dev_f64(x, dev) for x in (R_all, t_all, K, R_gt, t_gt))
     npz = torch.as_tensor(np.asarray(n_poses) if not isinstance(n_poses, torch.Tensor) else n_poses).to(device=dev, dtype=torch.int32).contiguous()
     S = torch.as_tensor(np.random.RandomState(seed).random_sample((n_support, 3)) - 0.5, device=dev)
@@ -116,8 +116,5 @@ def disambiguate_device(R_all, t_all, n_poses, K, R_gt, t_gt, n_support: int = 2
     idx = torch.empty((B,), dtype=torch.int32, device=dev)
     p = lambda x: C.c_void_p(x.data_ptr())  # noqa: E731
     with torch.cuda.device(dev):
-        rc = _lib.lib().cvxpnpl_disambiguate(B, p(Ra), p(ta), p(npz), p(Kd), p(Rg), p(tg), p(S), n_support, p(R), p(t), p(idx),
-                                             C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_disambiguate failed ({rc}): {_lib.last_error()}")
+        _call(_lib.lib(), "cvxpnpl_disambiguate", B, p(Ra), p(ta), p(npz), p(Kd), p(Rg), p(tg), p(S), n_support, p(R), p(t), p(idx), _stream(dev))
     return R, t, idx

@@ -149,21 +149,19 @@ def device_pnpl(batch, n_p, n_l, sigma=0.0, seed=42, K=K_KINECT, device=None):
     import torch
 
     from . import _lib
+    from .api import _call, _device_of, _stream
 
     if not torch.cuda.is_available():
         raise RuntimeError("device_pnpl needs a ROCm GPU")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = _device_of(device)
     Kd = torch.as_tensor(np.ascontiguousarray(K, dtype=np.float64), device=dev)
     mk = lambda *shape: torch.empty(shape, dtype=torch.float64, device=dev)  # noqa: E731
     out = {"pts_2d": mk(batch, n_p, 2), "pts_3d": mk(batch, n_p, 3), "line_2d": mk(batch, n_l, 2, 2), "line_3d": mk(batch, n_l, 2, 3),
            "R_gt": mk(batch, 3, 3), "t_gt": mk(batch, 3), "K": Kd}
     p = lambda t: C.c_void_p(t.data_ptr()) if t.numel() else C.c_void_p(0)  # noqa: E731
     with torch.cuda.device(dev):
-        rc = _lib.lib().cvxpnpl_synth_batch(batch, n_p, n_l, float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, p(Kd), p(out["pts_2d"]), p(out["pts_3d"]),
-                                            p(out["line_2d"]), p(out["line_3d"]), p(out["R_gt"]), p(out["t_gt"]),
-                                            C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_synth_batch failed ({rc}): {_lib.last_error()}")
+        _call(_lib.lib(), "cvxpnpl_synth_batch", batch, n_p, n_l, float(sigma), int(seed) & 0xFFFFFFFFFFFFFFFF, p(Kd), p(out["pts_2d"]), p(out["pts_3d"]),
+              p(out["line_2d"]), p(out["line_3d"]), p(out["R_gt"]), p(out["t_gt"]), _stream(dev))
     return out
 
 

@@ -123,6 +123,106 @@ def test_bad_arguments_are_rejected_without_gpu(L):
         assert rc == -1 and b"cvxpnpl_sample_minimal_sets: bad arguments" in L.cvxpnpl_last_error()
 
 
+def test_every_entry_point_refuses_a_malformed_call_with_its_code_and_message(L):
+    """One malformed call (or zero-size no-op) per int-returning entry point of the solver and the pose-VJP library and per distinct message,
+    with the return code and the text of *_last_error as the libraries gave them before their entry layer was stated once
+    (csrc/solver_entry.h): every row returns before any HIP call.  The rows run in order, so a refusal that writes no message (a null d_B
+    of the two assemblies, everything cvxpnpl_recover_multi_batch and cvxpnpl_pose_vjp_host refuse) and a no-op show the text of the row
+    before them."""
+    import math
+
+    from cvxpnpl_amd import _lib
+
+    G = _lib.grad_lib()
+    buf = (C.c_double * 64)()  # never dereferenced
+    P, N, nan = C.cast(buf, C.c_void_p), None, math.nan
+    DP, IP = C.cast(buf, C.POINTER(C.c_double)), C.cast(buf, C.POINTER(C.c_int32))
+    o, size = _lib.default_opts(), C.sizeof(_lib.Opts)
+    short = _lib.default_opts()
+    short.struct_size = size - 8
+    opt = lambda **kw: C.byref(_lib.default_opts(**kw))  # noqa: E731
+    big = 1 << 40
+    # well-formed argument lists (never called as they are) and the (position: value) changes that make a row
+    solve = [1, 4, P, P, 0, N, N, P, 0, C.byref(o), P, P, P, N, N, N, N, N]
+    cost = [1, P, P, C.byref(o), P, P, P, N, N, N, N, N]
+    asm = [1, 4, P, P, 0, N, N, P, 0, P, P, N]
+    large = asm[:11] + [P, 1 << 20, N]
+    subsets = [1, 4, P, P, P, P, P, P, N, N]
+    synth = [1, 4, 0, 0.5, 7, P, P, P, N, N, P, P, N]
+    errors = [1, P, P, P, P, P, P, N]
+    disamb = [1, P, P, P, P, P, P, P, 2, P, P, P, N]
+    rec_dev = [1, N, P, P, N, P, P, P, N]
+    rec_batch = [1, N, DP, DP, N, DP, DP, IP, 1]
+    pack = [1, P, P, P, P, N]
+    select = [1, P, P, P, P, P, 2, P, P, 2.0, P, P, P, P, N]
+    refit = [P, P, P, P, P, 2, P, P, 2.0, P, P, P, P, N]
+    score = [1, P, P, N, 5, P, 2, P, P, 2.0, P, N, N]
+    sample = [1, 10, P, P, 4, 1, N, P, P, N]
+    ipm = [1, P, 0, P, P, P, P, N]
+    copy = [P, P, 16, 4, N]
+    vjp = [1, 4, P, P, 0, N, N, P, 0, P, P, N, 1, N, N, N, N, N, N, P, N, N]
+    block = f"cvxpnpl: options block of {size - 8} bytes, this library's cvxpnpl_opts_t has {size} (cvxpnpl_default_opts / cvxpnpl_opts_size)"
+    rows = [
+        ("cvxpnpl_solve_batch", solve, {3: N}, -1, "cvxpnpl: bad arguments (batch=1 n_p=4 n_l=0)"),
+        ("cvxpnpl_solve_batch", solve, {0: -1}, -1, "cvxpnpl: bad arguments (batch=-1 n_p=4 n_l=0)"),
+        ("cvxpnpl_solve_batch", solve, {4: 2, 5: P}, -1, "cvxpnpl: bad arguments (batch=1 n_p=4 n_l=2)"),
+        ("cvxpnpl_solve_batch", solve, {0: 0, 2: N, 3: N, 7: N, 9: N, 10: N, 11: N, 12: N}, 0, "cvxpnpl: bad arguments (batch=1 n_p=4 n_l=2)"),
+        ("cvxpnpl_solve_batch", solve, {12: N}, -1, "cvxpnpl: R, t and status outputs are required"),
+        ("cvxpnpl_solve_batch", solve, {0: big}, -1, "cvxpnpl: batch too large for one launch"),
+        ("cvxpnpl_solve_batch", solve, {9: C.byref(short)}, -1, block),
+        ("cvxpnpl_solve_batch", solve, {9: opt(variant=7)}, -1, "cvxpnpl: bad options"),
+        ("cvxpnpl_solve_batch", solve, {9: opt(layout=99)}, -1, "cvxpnpl: bad options (layout 99 is not one of CVXPNPL_LAYOUT_*)"),
+        ("cvxpnpl_solve_cost_batch", cost, {2: N}, -1, "cvxpnpl_solve_cost_batch: bad arguments (batch=1)"),
+        ("cvxpnpl_solve_cost_batch", cost, {0: 0, 1: N, 2: N}, 0, "cvxpnpl_solve_cost_batch: bad arguments (batch=1)"),
+        ("cvxpnpl_solve_cost_batch", cost, {4: N}, -1, "cvxpnpl: R, t and status outputs are required"),
+        ("cvxpnpl_solve_cost_batch", cost, {0: big}, -1, "cvxpnpl: batch too large for one launch"),
+        ("cvxpnpl_solve_cost_batch", cost, {3: opt(variant=7)}, -1, "cvxpnpl: bad options"),
+        ("cvxpnpl_assemble_batch", asm, {7: N}, -1, "cvxpnpl: bad arguments (batch=1 n_p=4 n_l=0)"),
+        ("cvxpnpl_assemble_batch", asm, {0: 0, 7: N}, -1, "cvxpnpl: bad arguments (batch=0 n_p=4 n_l=0)"),  # (checked before the no-op)
+        ("cvxpnpl_assemble_batch", asm, {9: N}, -1, "cvxpnpl: bad arguments (batch=0 n_p=4 n_l=0)"),        # (no message of its own)
+        ("cvxpnpl_assemble_batch", asm, {0: 0}, 0, "cvxpnpl: bad arguments (batch=0 n_p=4 n_l=0)"),
+        ("cvxpnpl_assemble_large_batch", large, {1: 0}, -1, "cvxpnpl: bad arguments (batch=1 n_p=0 n_l=0)"),
+        ("cvxpnpl_assemble_large_batch", large, {9: N}, -1, "cvxpnpl: bad arguments (batch=1 n_p=0 n_l=0)"),  # (no message of its own)
+        ("cvxpnpl_assemble_large_batch", large, {0: 0}, 0, "cvxpnpl: bad arguments (batch=1 n_p=0 n_l=0)"),
+        ("cvxpnpl_assemble_large_batch", large, {0: 65536}, -1, "cvxpnpl_assemble_large_batch: at most 65535 problems per call (got 65536)"),
+        ("cvxpnpl_assemble_large_batch", large, {12: 8}, -1,
+         "cvxpnpl_assemble_large_batch: scratch of 480 bytes needed (cvxpnpl_assemble_large_scratch_bytes), got 8"),
+        ("cvxpnpl_assemble_subsets", subsets, {1: 0}, -1, "cvxpnpl_assemble_subsets: bad arguments"),
+        ("cvxpnpl_assemble_subsets", subsets, {0: 64 * 0x7fffffff + 1}, -1, "cvxpnpl_assemble_subsets: bad arguments"),
+        ("cvxpnpl_synth_batch", synth, {3: nan}, -1, "cvxpnpl_synth_batch: bad arguments"),
+        ("cvxpnpl_synth_batch", synth, {0: big}, -1, "cvxpnpl_synth_batch: too many records for one launch"),
+        ("cvxpnpl_pose_errors", errors, {6: N}, -1, "cvxpnpl_pose_errors: bad arguments"),
+        ("cvxpnpl_disambiguate", disamb, {8: -1}, -1, "cvxpnpl_disambiguate: bad arguments"),
+        ("cvxpnpl_recover_multi_device", rec_dev, {2: N}, -1, "cvxpnpl_recover_multi_device: bad arguments"),
+        ("cvxpnpl_stream_write_value", [N, 1, N], {}, -1, "cvxpnpl_stream_write_value: null flag"),
+        ("cvxpnpl_stream_wait_value", [N, 1, N], {}, -1, "cvxpnpl_stream_wait_value: null flag"),
+        ("cvxpnpl_stream_wait_gave_up", [N, 0, N], {}, -1, "cvxpnpl_stream_wait_gave_up: null flag"),
+        ("cvxpnpl_stream_wait_value_bounded", [N, 1, 4, N], {}, -1, "cvxpnpl_stream_wait_value: null flag"),  # (the text of the unbounded wait)
+        ("cvxpnpl_pack_results", pack, {0: big}, -1, "cvxpnpl_pack_results: batch too large for one launch"),
+        ("cvxpnpl_select_best", select, {0: 0}, -1, "cvxpnpl_select_best: bad arguments"),
+        ("cvxpnpl_refit_update", refit, {8: nan}, -1, "cvxpnpl_refit_update: bad arguments"),
+        ("cvxpnpl_score_hypotheses", score, {9: -1.0}, -1, "cvxpnpl_score_hypotheses: bad arguments"),
+        ("cvxpnpl_score_hypotheses", score, {0: 1 << 50}, -1, "cvxpnpl_score_hypotheses: too many hypotheses for one launch"),
+        ("cvxpnpl_sample_minimal_sets", sample, {0: 1 << 50}, -1, "cvxpnpl_sample_minimal_sets: too many hypotheses for one launch"),
+        ("cvxpnpl_ipm_batch", ipm, {2: 2}, -1, "cvxpnpl_ipm_batch: bad arguments"),
+        ("cvxpnpl_ipm_batch", ipm, {0: big}, -1, "cvxpnpl_ipm_batch: bad arguments"),
+        ("cvxpnpl_calibration_copy", copy, {3: 3}, -1, "cvxpnpl_calibration_copy: bad arguments"),
+        ("cvxpnpl_recover_multi_batch", rec_batch, {2: N}, -1, "cvxpnpl_calibration_copy: bad arguments"),  # (no message of its own)
+        ("cvxpnpl_pose_vjp_batch", vjp, {19: N}, -1, "cvxpnpl_pose_vjp_batch: bad arguments (batch=1 n_p=4 n_l=0)"),
+        ("cvxpnpl_pose_vjp_batch", vjp, {0: 0, 7: N}, -1, "cvxpnpl_pose_vjp_batch: bad arguments (batch=0 n_p=4 n_l=0)"),
+        ("cvxpnpl_pose_vjp_batch", vjp, {0: 0, 9: N, 10: N, 19: N}, 0, "cvxpnpl_pose_vjp_batch: bad arguments (batch=0 n_p=4 n_l=0)"),
+        ("cvxpnpl_pose_vjp_batch", vjp, {0: 1 << 50}, -1, "cvxpnpl_pose_vjp_batch: batch too large for one launch"),
+        ("cvxpnpl_pose_vjp_batch", vjp, {0: 65535, 1: 0x7fffffff}, -1, "cvxpnpl_pose_vjp_batch: too many correspondences for one launch"),
+        ("cvxpnpl_pose_vjp_host", vjp[:-1] + [1], {7: N}, -1, "cvxpnpl_pose_vjp_batch: too many correspondences for one launch"),  # (no message)
+    ]
+    for i, (name, args, change, rc, text) in enumerate(rows):
+        grad = name.startswith("cvxpnpl_pose_vjp")
+        args = [change.get(k, a) for k, a in enumerate(args)]
+        got = getattr(G if grad else L, name)(*args)
+        said = (G.cvxpnpl_grad_last_error if grad else L.cvxpnpl_last_error)().decode()
+        assert (got, said) == (rc, text), (i, name, change)
+
+
 def test_product_fails_loudly_without_gpu():
     import torch
 
