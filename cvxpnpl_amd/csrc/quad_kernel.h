@@ -281,6 +281,8 @@ __device__ __forceinline__ void quad_proj(double *L, const OWN &w, double *X, do
 // row; tools/microbench/eig16x.hip: -1 % / -6 % per sweep in single / double precision).  t = s / c is still returned: the norms are
 // updated incrementally, |own'|^2 = |own|^2 - t gam, |other'|^2 = |other|^2 + t gam.
 // Single precision throughout (see the eigen-solve in solve_quad_kernel): v_rsq_f32 is good to 1 ulp.
+// Domain: as cvx::jacobi_cs(float) -- the guard 1e-37 is small beside h2 because the callers rotate only when gam^2 > 1e-30 |own|^2 |other|^2
+// and the squared norms are >= (0.5 |W|_F)^2 with |W|_F >= 1; squared norms of 1e-5 and less would make this no rotation.
 __device__ __forceinline__ void pair_cs(float d, float gam, bool rot, bool tie_neg, float &c, float &s, float &t)
 {
     const float g2 = 2.0f * gam;

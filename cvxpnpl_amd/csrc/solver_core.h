@@ -188,8 +188,21 @@ static_assert(tri_parity_uniform(), "every equality triple must have a single pa
 // tiny helpers
 
 // reciprocal and reciprocal square root: on the device the hardware seed (v_rcp_f64 /
-// v_rsq_f64) plus two Newton steps (<= 1-2 ulp) instead of the IEEE expansion; every use
-// below is either self-correcting (Newton iterations) or followed by an explicit check.
+// v_rsq_f64) plus a refinement instead of the IEEE expansion -- ONE third-order step in the
+// solver library's unit, TWO Newton steps in csrc/lane_kernel.hip's (CVX_REFINE_NEWTON2),
+// <= 1-2 ulp either way; every use below is either self-correcting (Newton iterations) or
+// followed by an explicit check.  Both units and cvxw::fast_rcp are held to 2 ulp on every
+// binade 2^-1000 ... 2^1000 by tests/test_device_arithmetic_gpu.py (measured: rcp 0.50 ulp,
+// rsqrt_ 0.75 / 0.62 ulp, sqrt_fast 0.97 ulp).
+// Special arguments (same test; the callers' guards are listed in its docstring).  The
+// refinement multiplies 0 by inf, so the device branch returns NaN where IEEE has inf or 0:
+//                   +0    -0    +inf  -inf  NaN   x < 0   5e-324 (least subnormal)   other subnormals, |x| > 2^1000
+//   rcp     device  NaN   NaN   NaN   NaN   NaN   1 / x   NaN (1 / x overflows)      1 / x to 2 ulp
+//           host    +inf  -inf  +0    -0    NaN   1 / x   +inf                       1 / x
+//   rsqrt_  device  NaN   NaN   NaN   NaN   NaN   NaN     ok (Newton-2 unit: x 2.25) 1 / sqrt(x) to 2 ulp
+//           host    +inf  -inf  +0    NaN   NaN   NaN     ok                         1 / sqrt(x)
+//   sqrt_fast dev.  0     0     NaN   0     0     0       ok (Newton-2 unit: x 2.25) sqrt(x) to 2 ulp
+//           host    +0    -0    +inf  NaN   NaN   NaN     ok                         sqrt(x)
 CVX_HD double rcp(double x)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -508,8 +521,13 @@ CVX_HD void jacobi_cs(double al, double be, double gam, bool rot, double &c, dou
 #if defined(__HIP_DEVICE_COMPILE__)
     // tan(theta) in single precision (one v_rsq_f32 + one v_rcp_f32): an angle that is right to
     // ~1e-7 still annihilates g_p . g_q to 1e-7 of its size per rotation, far below the
-    // sweep tolerance.  cos(theta) then comes from a float seed refined by one double Newton
-    // step (|c^2 + s^2 - 1| ~ 1e-14), so the accumulated rotation stays orthogonal.
+    // sweep tolerance.  cos(theta) then comes from a float seed refined by one third-order double
+    // step, z (1 + e + 1.5 e^2) with e = (1 - x z^2) / 2 (what is left is 2.5 e^3 ~ 1e-20: c^2 + s^2 = 1 to rounding), so the
+    // accumulated rotation stays orthogonal.  A plain Newton step (until the device-arithmetic tests: z (1 + e), one FMA less) leaves
+    // -1.5 e^2, up to 1.8e-14 and ALWAYS from below: every rotation shrank its two columns by that much, and after an eigen-solve the
+    // eigenvalues sqrt(n2) - sigma and the positive part built from them were low by up to 1.2e-12 at sigma ~ 20 -- ten times the
+    // 2e-14 |lam|max that the host build and the float64 angles meet (tests/test_device_arithmetic_gpu.py).
+    // Domain: see jacobi_cs(float) below for the 1e-37 guard.
     const float df = (float)d, gf = (float)g2;
     const float h2 = df * df + gf * gf + 1e-37f;
     const float hf = h2 * __builtin_amdgcn_rsqf(h2);
@@ -518,7 +536,7 @@ CVX_HD void jacobi_cs(double al, double be, double gam, bool rot, double &c, dou
     t = rot ? (double)tf : 0.0;
     const double x = 1.0 + t * t;
     double z = (double)__builtin_amdgcn_rsqf((float)x);
-    { double hh = 0.5 * x * z; double e = fma(-hh, z, 0.5); z = fma(z, e, z); }
+    { double hh = 0.5 * x * z; double e = fma(-hh, z, 0.5); z = fma(z * e, fma(1.5, e, 1.0), z); }
     c = z;
 #else
     const double h = sqrt(d * d + g2 * g2 + 1e-290);
@@ -738,6 +756,11 @@ CVX_HD void jacobi_cs(float al, float be, float gam, bool rot, float &c, float &
     const float d = be - al, g2 = 2.0f * gam;
 #if defined(__HIP_DEVICE_COMPILE__)
     // half-angle form (two v_rsq_f32 in a row instead of rsq -> rcp -> rsq): cos 2th = |d| / h, c^2 = (1 + cos 2th) / 2
+    // Domain: the guard 1e-37 must be small beside h2, else this is no rotation (d = 0, gam -> 0: c -> 0.71, s -> 0).  The callers
+    // rotate only when gam^2 > 1e-30 al be, and al, be >= (0.5 |W|_F)^2 (sigma = 1.5 |W|_F), so h2 > 2.5e-31 |W|_F^4: 2.5e6 times
+    // the guard at |W|_F = 1, the smallest norm an iterate has (W0 = e9 e9^T; measured 1 ... 20), where it costs c^2 + s^2 at most
+    // 2e-7.  Squared column norms of 1e-5 and less are outside the domain.  (tests/test_device_arithmetic.py has the argument,
+    // tests/test_device_arithmetic_gpu.py a test at that edge.)
     const float h2 = d * d + g2 * g2 + 1e-37f;
     const float ih = __builtin_amdgcn_rsqf(h2);
     const float c2 = fmaf(0.5f * fabsf(d), ih, 0.5f);

@@ -229,6 +229,61 @@ def pospart(W55):
     return Wp, lam, s
 
 
+def scalar(name, x):
+    """the HOST branch of cvx::rcp | rsqrt_ | sqrt_fast on x [n]"""
+    f = lib().hs_scalar
+    f.argtypes = [C.c_int, C.c_double]
+    f.restype = C.c_double
+    op = ("rcp", "rsqrt_", "sqrt_fast").index(name)
+    return np.array([f(op, float(v)) for v in np.asarray(x, dtype=np.float64).reshape(-1)])
+
+
+def pospart_f32(W55):
+    """the same on single-precision columns (cvx::EigF)"""
+    W = np.ascontiguousarray(W55, dtype=np.float64)
+    Wp, lam = np.zeros(55), np.zeros(10)
+    s = lib().hs_pospart_f32(_p(W), _p(Wp), _p(lam))
+    return Wp, lam, s
+
+
+def pospart_batch(W55, mode="f64"):
+    """W [n, 55] -> Wp [n, 55], lam [n, 10], sweeps [n]; mode f64 | exact (the host build is float64 throughout: the same) | f32 (EigF)"""
+    W = np.ascontiguousarray(W55, dtype=np.float64).reshape(-1, 55)
+    r = [pospart_f32(w) if mode == "f32" else pospart(w) for w in W]
+    return np.array([a[0] for a in r]), np.array([a[1] for a in r]), np.array([a[2] for a in r], dtype=np.int32)
+
+
+def polar3_batch(M, iters=12):
+    """cvx::polar3 on M [n, 3, 3] (row-major) -> [n, 3, 3]"""
+    M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 9)
+    R = np.zeros_like(M)
+    lib().hs_polar3.argtypes = [_dp, _dp, C.c_int]
+    lib().hs_polar3.restype = None
+    for m, r in zip(M, R):
+        lib().hs_polar3(_p(m), _p(r), int(iters))
+    return R.reshape(-1, 3, 3)
+
+
+def near_rotation_batch(M):
+    """cvx::near_rotation on M [n, 3, 3] -> [n, 3, 3]"""
+    M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 9)
+    R = np.zeros_like(M)
+    lib().hs_near_rotation.restype = None
+    for m, r in zip(M, R):
+        lib().hs_near_rotation(_p(m), _p(r))
+    return R.reshape(-1, 3, 3)
+
+
+def inv3_batch(M):
+    """cvx::inv3 on M [n, 3, 3] -> inverse [n, 3, 3], det [n]"""
+    M = np.ascontiguousarray(M, dtype=np.float64).reshape(-1, 9)
+    Mi, det = np.zeros_like(M), np.zeros(len(M))
+    lib().hs_inv3.restype = None
+    for k in range(len(M)):
+        lib().hs_inv3(_p(M[k]), _p(Mi[k]), _p(det[k:k + 1]))
+    return Mi.reshape(-1, 3, 3), det
+
+
 def dual_lambda(R, rhs, symm=False):
     R = np.ascontiguousarray(R, dtype=np.float64)
     rhs = np.ascontiguousarray(rhs, dtype=np.float64)

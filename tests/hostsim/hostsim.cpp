@@ -157,7 +157,23 @@ int hs_pospart(const double *W, double *Wp, double *lam)
     return s;
 }
 
+// the same hook on single-precision columns (EigF): the host figure tests/devsim's device instantiation is held against
+int hs_pospart_f32(const double *W, double *Wp, double *lam)
+{
+    cvx::EigF e;
+    cvx::eig_load(e, W);
+    int s = cvx::eig_solve(e, 30, 1e-30);
+    cvx::eig_pospart(e, Wp);
+    for (int j = 0; j < 10; ++j) lam[j] = sqrt((double)e.n2[j]) - e.sigma;
+    return s;
+}
+
+// the host branches of the scalar helpers (0 rcp, 1 rsqrt_, 2 sqrt_fast): the other column of the special-argument table of tests/devsim
+double hs_scalar(int op, double x) { return op == 0 ? cvx::rcp(x) : (op == 1 ? cvx::rsqrt_(x) : cvx::sqrt_fast(x)); }
+
 void hs_polar3(const double *M, double *R, int iters) { cvx::polar3(M, R, iters); }
+void hs_near_rotation(const double *M, double *R) { cvx::near_rotation(M, R); }
+void hs_inv3(const double *M, double *Mi, double *det) { cvx::inv3(M, Mi, *det); }
 }
 
 // the solve at the cost seam (cvxpnpl_solve_cost_batch), host pointers; variant: cvx::VAR_FULL / cvx::VAR_RC

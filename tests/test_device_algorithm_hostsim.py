@@ -10,6 +10,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import hostsim  # noqa: E402
+import device_arithmetic_cases as cases  # noqa: E402  (the bodies that tests/test_device_arithmetic_gpu.py also runs on the device build)
+from device_arithmetic_cases import pack55, unpack55  # noqa: E402,F401
 from cvxpnpl_amd import synth  # noqa: E402
 
 # rotation geodesic / relative translation tolerance vs the oracle (float64 path; the oracle's
@@ -18,76 +20,19 @@ TOL_ROT = 1e-6
 TOL_T = 1e-6
 
 
-def unpack55(v):
-    M = np.zeros((10, 10))
-    k = 0
-    for i in range(10):
-        for j in range(i, 10):
-            M[i, j] = M[j, i] = v[k]
-            k += 1
-    return M
-
-
-def pack55(M):
-    return np.array([M[i, j] for i in range(10) for j in range(i, 10)])
-
-
 def test_assembly_matches_reference_g3(golden):
     """Gram/Schur assembly == the reference's A^T A and B (captured from the reference)."""
-    rc, B, Q = hostsim.assemble(golden["ex_pnp_pts2d"], golden["ex_pnp_pts3d"], None, None, golden["ex_pnp_K"])
-    A = golden["g3_pnp_A"]
-    assert rc == 0
-    np.testing.assert_allclose(B, golden["g3_pnp_B"], atol=1e-11)
-    np.testing.assert_allclose(Q, A.T @ A, atol=1e-13)
-    rc, B, Q = hostsim.assemble(None, None, golden["ex_pnl_line2d"], golden["ex_pnl_line3d"], golden["ex_pnl_K"])
-    A = golden["g3_pnl_A"]
-    np.testing.assert_allclose(B, golden["g3_pnl_B"], atol=1e-11)
-    np.testing.assert_allclose(Q, A.T @ A, atol=1e-13)
-    rc, B, Q = hostsim.assemble(golden["ex_pnpl_pts2d"], golden["ex_pnpl_pts3d"], golden["ex_pnpl_line2d"], golden["ex_pnpl_line3d"],
-                                golden["ex_pnpl_K"])
-    A = golden["g3_pnpl_A"]
-    np.testing.assert_allclose(B, golden["g3_pnpl_B"], atol=1e-11)
-    np.testing.assert_allclose(Q, A.T @ A, atol=1e-13)
-    # the cost vector handed to scs: c = vech(Q, 2) (cvxpnpl.py:486)
-    Q10 = np.zeros((10, 10))
-    Q10[:9, :9] = Q
-    c = np.array([(1 if i == j else 2) * Q10[i, j] for j in range(10) for i in range(j, 10)])
-    np.testing.assert_allclose(c, golden["g3_pnpl_c"], atol=1e-13)
+    cases.check_assembly_matches_reference_g3(hostsim, golden)
 
 
 def test_affine_projection_matches_reference_constraints(golden):
     """The closed-form projector == dense projection onto {x : E x = b} built from the
     reference's own _A, _b (first 22 rows), in the Frobenius geometry of symmetric matrices."""
-    A, b = golden["g4_A"][:22], golden["g4_b"][:22]
-    # reference x = vech (column-major lower) == our packing (row-major upper); weights: off-diagonals count twice
-    wgt = np.array([1.0 if i == j else 2.0 for i in range(10) for j in range(i, 10)])
-    Aw = A / wgt  # <A_i, Z>_F = sum wgt * a_ij z_ij  -> a = A / wgt
-    rs = np.random.RandomState(0)
-    for homog in (False, True):
-        x = rs.normal(size=55)
-        bb = np.zeros(22) if homog else b
-        # minimise sum wgt (y - x)^2 s.t. A y = bb
-        Wi = 1.0 / wgt
-        lam = np.linalg.lstsq(A @ (Wi[:, None] * A.T), A @ x - bb, rcond=None)[0]
-        y = x - Wi * (A.T @ lam)
-        np.testing.assert_allclose(hostsim.proj_affine(x, homog), y, atol=1e-13)
-        np.testing.assert_allclose(A @ hostsim.proj_affine(x, homog), bb, atol=1e-13)
+    cases.check_affine_projection_matches_reference_constraints(hostsim, golden)
 
 
 def test_psd_projection_matches_numpy():
-    rs = np.random.RandomState(1)
-    for trial in range(20):
-        M = rs.normal(size=(10, 10))
-        M = M + M.T
-        if trial % 4 == 0:  # clustered / rank deficient spectra
-            q, _ = np.linalg.qr(rs.normal(size=(10, 10)))
-            M = (q * np.array([3, 1, 1, 1e-9, 0, 0, -1e-9, -1, -1, -2.0])) @ q.T
-        w, v = np.linalg.eigh(M)
-        Mp = (v * np.maximum(w, 0)) @ v.T
-        Wp, lam, sweeps = hostsim.pospart(pack55(M))
-        np.testing.assert_allclose(unpack55(Wp), Mp, atol=2e-14 * max(1.0, np.abs(w).max()))
-        np.testing.assert_allclose(np.sort(lam), w, atol=2e-14 * max(1.0, np.abs(w).max()))
-        assert sweeps <= 12
+    cases.check_psd_projection_matches_numpy(hostsim)
 
 
 CASES = [  # (n_p, n_l, sigma, batch)
@@ -178,73 +123,16 @@ def test_planar_scenes_certify_the_two_fold_pair_early():
     assert np.median(hs["iters"]) <= 20
 
 
-def _sym_from_row(a):
-    """row of the reference's equality block (coefficients over vech) -> symmetric 10x10 with <A, Z>_F = a . vech(Z)"""
-    M = np.zeros((10, 10))
-    k = 0
-    for i in range(10):
-        for j in range(i, 10):
-            M[i, j] = M[j, i] = a[k] if i == j else a[k] / 2.0
-            k += 1
-    return M
-
-
 def test_closed_form_dual_multipliers_match_reference_constraints(golden):
     """dual_lambda: the minimum-norm correction dS in span{A_i} with dS z = rhs, computed through the constant
     10x10 system in the frame of R, equals the dense least-norm solution built from the reference's own
     _A (cvxpnpl.py:387-451, golden G4) -- for arbitrary rotations."""
-    A = golden["g4_A"][:22]
-    mats = [_sym_from_row(a) for a in A]
-    # orthonormal basis of span{A_i} in the Frobenius inner product
-    V = np.array([m.reshape(-1) for m in mats]).T  # 100 x 22
-    u, sv, _ = np.linalg.svd(V, full_matrices=False)
-    basis = [u[:, k].reshape(10, 10) for k in range(22) if sv[k] > 1e-10 * sv[0]]
-    assert len(basis) == 21  # the 22 rows have one dependency: row sums and column sums of the diagonal block
-    rs = np.random.RandomState(3)
-    for trial in range(6):
-        Rm, _ = np.linalg.qr(rs.normal(size=(3, 3)))
-        if np.linalg.det(Rm) < 0:
-            Rm[:, 0] = -Rm[:, 0]
-        z = np.concatenate([Rm.T.reshape(-1), [1.0]])  # vec_colmajor(R); 1
-        # a consistent right-hand side: rhs = G z with G in the span
-        G = sum(c * b for c, b in zip(rs.normal(size=21), basis))
-        rhs = G @ z
-        # dense: dS = sum c_k B_k, minimise |c| s.t. (sum c_k B_k) z = rhs
-        Mz = np.array([b @ z for b in basis]).T  # 10 x 21, rank 7: its left null space is the tangent space of SO(3) at R
-        assert np.linalg.matrix_rank(Mz, tol=1e-9) == 7
-        c = np.linalg.pinv(Mz, rcond=1e-10) @ rhs
-        dS_ref = sum(ck * b for ck, b in zip(c, basis))
-        assert np.abs(dS_ref @ z - rhs).max() < 1e-12
-        lam = hostsim.dual_lambda(Rm, rhs)
-        E = 0.5 * (np.outer(lam, z) + np.outer(z, lam))
-        dS = unpack55(pack55(E) - hostsim.proj_affine(pack55(E), True))  # P_range(E) = E - P_null(E)
-        np.testing.assert_allclose(dS, dS_ref, atol=1e-12)
+    cases.check_closed_form_dual_multipliers_match_reference_constraints(hostsim, golden)
 
 
 def test_reuse_test_is_a_polar_factor_test():
     """rounds_to(v, Rp): true when the polar factor of mat(v[:9] / v[9]) is within ~0.16 rad of Rp."""
-    rs = np.random.RandomState(4)
-
-    def rot(axis, ang):
-        axis = axis / np.linalg.norm(axis)
-        Kx = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
-        return np.eye(3) + np.sin(ang) * Kx + (1 - np.cos(ang)) * Kx @ Kx
-
-    for trial in range(50):
-        Rp, _ = np.linalg.qr(rs.normal(size=(3, 3)))
-        if np.linalg.det(Rp) < 0:
-            Rp[:, 0] = -Rp[:, 0]
-        ang = rs.uniform(0.0, 0.5)
-        P = np.eye(3) * rs.uniform(0.6, 1.0) + 0.05 * np.diag(rs.normal(size=3))  # symmetric positive definite stretch
-        M0 = Rp @ rot(rs.normal(size=3), ang) @ P
-        s = rs.uniform(0.5, 2.0) * (1 if trial % 2 else -1)
-        v = np.concatenate([M0.T.reshape(-1), [1.0]]) * s  # any multiple of [vec(M0); 1]
-        ok, d0 = hostsim.rounds_to(v, Rp)
-        assert d0 > 0
-        if ang < 0.10:
-            assert ok
-        if ang > 0.25:
-            assert not ok
+    cases.check_reuse_test_is_a_polar_factor_test(hostsim)
 
 
 def test_planar_scene_in_a_general_frame_is_solved_in_the_canonical_one():
@@ -293,22 +181,8 @@ def test_assembly_far_from_the_world_origin(orc):
     import hostsim
     from cvxpnpl_amd import synth
 
-    d = synth.make_pnpl(12, 6, 3, 0.5, seed=17)
-    c = np.random.RandomState(2).normal(size=(12, 1, 3)) * 600.0
-    d["pts_3d"] = d["pts_3d"] + c
-    d["line_3d"] = d["line_3d"] + c[:, None]
-    worst_q = worst_b = 0.0
-    for i in range(12):
-        (c1, c2, c3), (n1, n2, n3) = orc.point_constraints(d["pts_2d"][i], d["pts_3d"][i], d["K"])
-        cl, nl = orc.line_constraints(d["line_2d"][i], d["line_3d"][i], d["K"])
-        B, A = orc.eliminate(np.vstack((c1, c2, c3, cl)), np.vstack((n1, n2, n3, nl)))
-        rc, Bh, Qh = hostsim.assemble(d["pts_2d"][i], d["pts_3d"][i], d["line_2d"][i], d["line_3d"][i], d["K"])
-        assert rc == 0
-        Q = A.T @ A
-        worst_q = max(worst_q, np.abs(Qh - Q).max() / np.abs(Q).max())
-        worst_b = max(worst_b, np.abs(Bh - B).max() / np.abs(B).max())
-    # (the reference's own A^T A carries the cancellation of C - N B at this offset: ~1e-10 relative)
-    assert worst_q < 1e-8 and worst_b < 1e-9, (worst_q, worst_b)
+    d = cases.far_origin_problem()
+    cases.check_assembly_far_from_the_world_origin(hostsim, orc, d)
     h = hostsim.solve_batch(d["pts_2d"], d["pts_3d"], d["line_2d"], d["line_3d"], d["K"])
     o = orc.pnpl_batch(d["pts_2d"], d["line_2d"], d["pts_3d"], d["line_3d"], d["K"], eps=1e-11, max_iters=200000)
     ok = (h["status"] == 0) & (o["n_poses"] == 1)
@@ -454,23 +328,4 @@ def test_gram_sums_are_taken_about_a_robust_centre():
     50 000 scene sizes away the assembled cost agrees to 1e-11 of its largest entry wherever that point stands in the list, under
     either rule -- such a point dominates the cost whatever the centre): the order of the correspondences does not matter, and
     points, lines, mixed records and fewer than three records all go through it."""
-    import hostsim
-    from cvxpnpl_amd import synth
-
-    d = synth.make_pnp(1, 12, 0.5, seed=8)
-    p2, p3 = d["pts_2d"][0].copy(), d["pts_3d"][0].copy()
-    p3[0] += np.array([3.0e4, -2.0e4, 1.0e4])  # 50 000 scene sizes away
-    outs = []
-    for pos in (0, 1, 2, 11):
-        idx = list(range(1, 12))
-        idx.insert(pos, 0)
-        _, B, Q = hostsim.assemble(p2[idx], p3[idx], None, None, d["K"])
-        outs.append((B, Q))
-    Q0 = outs[-1][1]  # outlier last: the centre is a scene point whatever the rule
-    for B, Q in outs[:-1]:
-        assert np.abs(Q - Q0).max() <= 1e-11 * np.abs(Q0).max()
-        assert np.abs(B - outs[-1][0]).max() <= 1e-9 * np.abs(outs[-1][0]).max()
-    # lines, mixed records and fewer than three records go through the same rule
-    dl = synth.make_pnpl(1, 1, 3, 0.0, seed=3)
-    rc, B, Q = hostsim.assemble(dl["pts_2d"][0], dl["pts_3d"][0], dl["line_2d"][0], dl["line_3d"][0], dl["K"])
-    assert rc == 0 and np.isfinite(Q).all()
+    cases.check_gram_sums_are_taken_about_a_robust_centre(hostsim)
