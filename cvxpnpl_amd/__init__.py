@@ -17,3 +17,5 @@ from .refine_robust_auto import (RobustAutoResult, RobustCovariance, RobustScale
 from .refine_robust_grad import refine_pose_batch_robust_diff, refine_vjp_robust, refine_vjp_robust_host, refine_vjp_scenes_robust  # noqa: F401
 from .refine_grad import pose_passthrough, refine_pose_batch_diff, refine_vjp, refine_vjp_host, refine_vjp_scenes  # noqa: F401
 from .ransac import ransac_pnl, ransac_pnl_batch, ransac_pnp_batch, ransac_pnpl, ransac_pnpl_batch  # noqa: F401
+from .ransac import (adaptive_init_msac, msac_gain_host, score_active_msac, score_scenes_msac, select_scenes_msac,  # noqa: F401
+                     update_active_msac)

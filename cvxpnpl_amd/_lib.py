@@ -373,6 +373,28 @@ def refine_robust_auto_lib():
     return _load(REFINE_ROBUST_AUTO_LIB_PATH, REFINE_ROBUST_AUTO_EXPORTS, _refine_robust_auto_argtypes)
 
 
+# MSAC scoring for RANSAC over many scenes (include/cvxpnpl_amd_ransac_msac.h): the thirteenth library
+RANSAC_MSAC_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_msac.so")
+RANSAC_MSAC_EXPORTS = ("cvxpnpl_ransac_msac_score_scenes", "cvxpnpl_ransac_msac_score_active", "cvxpnpl_ransac_msac_select_scenes",
+                       "cvxpnpl_ransac_msac_init", "cvxpnpl_ransac_msac_update", "cvxpnpl_ransac_msac_score_host", "cvxpnpl_ransac_msac_last_error")
+
+
+def _ransac_msac_argtypes(L):
+    p, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    L.cvxpnpl_ransac_msac_score_scenes.argtypes = [i64, i32, p, i64, p, p, p, C.c_uint32, p, i32, p, p, f64, p, p, p]
+    L.cvxpnpl_ransac_msac_score_active.argtypes = [i64, i64, p, i32, p, i64, p, p, p, C.c_uint32, p, i32, p, p, f64, p, p, p]
+    L.cvxpnpl_ransac_msac_select_scenes.argtypes = [i64, i32, p, i64, p, p, p, p, p, i32, p, p, f64, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_msac_init.argtypes = [i64, p, p]
+    L.cvxpnpl_ransac_msac_update.argtypes = [i64, i64, p, i32, i32, i32, f64, p, i64, p, p, p, p, p, p, i32, p, p, f64,
+                                             p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_msac_score_host.argtypes = [i64, i32, p, i64, p, p, p, C.c_uint32, p, i32, p, p, f64, p, p, i32]
+
+
+def ransac_msac_lib():
+    """Load libcvxpnpl_amd_ransac_msac.so (loudly)."""
+    return _load(RANSAC_MSAC_LIB_PATH, RANSAC_MSAC_EXPORTS, _ransac_msac_argtypes)
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

@@ -195,6 +195,25 @@ def _chk_state(sc, st):
         raise ValueError("state.active and state.active_next are the same buffer")
 
 
+def _chk_state_msac(sc, st):
+    """st: ransac.AdaptiveState with best_gain (adaptive_init_msac): the state, and best_gain [F] float64 beside best."""
+    _chk_state(sc, st)
+    if getattr(st, "best_gain", None) is None:
+        raise ValueError("state.best_gain is missing: the state of an MSAC call comes from adaptive_init_msac")
+    _chk(st.best_gain, "state.best_gain", torch.float64, (sc.F,), sc.device)
+
+
+def _chk_gain(sc, gain, n):
+    """The gains of n hypotheses: float64 [n] on the scenes' device."""
+    return _chk(gain, "gain", torch.float64, (n,), sc.device)
+
+
+def _chk_scoring(scoring):
+    if scoring not in ("count", "msac"):
+        raise ValueError(f"scoring must be 'count' or 'msac', got {scoring!r}")
+    return scoring
+
+
 def _chk_pool_full(pool_full):
     if isinstance(pool_full, bool) or not isinstance(pool_full, (int, _np.integer)) or not 0 <= int(pool_full) <= 0x7FFFFFFF:
         raise ValueError(f"pool_full must be an int >= 0 (and below 2^31), got {pool_full!r}")

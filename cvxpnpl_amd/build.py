@@ -17,7 +17,7 @@ DEPS = [SRC, HOST_SRC, LANE_SRC, *SOLVER_ENTRY_HEADERS, os.path.join(HERE, "csrc
         os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd.h")]
 
 
-RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the five RANSAC entry files share
+RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the six RANSAC entry files share
 
 
 def hipcc():
@@ -211,6 +211,21 @@ def refine_robust_auto_compile_cmd(out=REFINE_ROBUST_AUTO_OUT):
     return grad_compile_cmd(out)[:-2] + [REFINE_ROBUST_AUTO_SRC, REFINE_ROBUST_AUTO_HOST_SRC]
 
 
+# MSAC scoring for RANSAC over many scenes, the hypothesis selected by its truncated quadratic cost (include/cvxpnpl_amd_ransac_msac.h): the
+# thirteenth library, the flags of the third.  (Named apart from the twelve pairs above, whose set tests/test_build_deps.py pins;
+# tests/test_ransac_msac_library.py holds this list against the include closure of its source.)
+RANSAC_MSAC_SRC = os.path.join(HERE, "csrc", "ransac_msac_hip.hip")
+RANSAC_MSAC_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_msac.so")
+RANSAC_MSAC_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_msac.resources.txt")
+RANSAC_MSAC_SOURCES = [RANSAC_MSAC_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_msac_kernel.h"), os.path.join(HERE, "csrc", "ransac_msac_core.h"),
+                       os.path.join(HERE, "csrc", "ransac_adaptive_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                       os.path.join(HERE, "csrc", "host_pool.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_msac.h")]
+
+
+def ransac_msac_command(out=RANSAC_MSAC_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_MSAC_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -273,8 +288,12 @@ def build_refine_robust_auto(force=False, verbose=False):
     return _build_one(REFINE_ROBUST_AUTO_OUT, REFINE_ROBUST_AUTO_RESOURCES, REFINE_ROBUST_AUTO_DEPS, refine_robust_auto_compile_cmd(), force, verbose)
 
 
+def build_ransac_msac(force=False, verbose=False):
+    return _build_one(RANSAC_MSAC_OUT, RANSAC_MSAC_RESOURCES, RANSAC_MSAC_SOURCES, ransac_msac_command(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All twelve libraries; returns the solver's (OUT)."""
+    """All thirteen libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -287,6 +306,7 @@ def build(force=False, verbose=False):
     build_ransac_guided(force, verbose)
     build_ransac_pnpl_adaptive(force, verbose)
     build_refine_robust_auto(force, verbose)
+    build_ransac_msac(force, verbose)
     return OUT
 
 

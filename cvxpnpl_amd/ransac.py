@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from ._ransac_args import (_call, _chk, _chk_active, _chk_budget, _chk_pnpl_scenes, _chk_pool_full, _chk_round, _chk_scenes, _chk_state,  # noqa: F401
+                           _chk_gain, _chk_scoring, _chk_state_msac,
                            _chk_refit, _cost_outputs, _data_args, _poses, _resolve_seeds, _sample_outputs, _scene_args, _seed_words, _seeds_dev, _usable_mask)
 from .api import _ptr, _require_gpu
 from .api import assemble_subsets, pnp_batch, refit_update, sample_minimal_sets, score_hypotheses, select_best, solve_cost_batch
@@ -236,7 +237,8 @@ def refit_update_scenes(sc: Scenes, fit, fit_count, thresh, R, t, head, mask):
 class AdaptiveState:
     """What an adaptive call keeps over its rounds, on the scenes' device: active, active_next [F] int32 (the first n entries count),
     n_active [1] int32, done [F] int32, R [F,3,3], t [F,3], head [F,4] int32, best [F] int32 (the count of the running winner), mask
-    [total] uint8, hyp_used [F] int32.  Built by adaptive_init."""
+    [total] uint8, hyp_used [F] int32.  Built by adaptive_init.  best_gain: None, or -- an MSAC call, adaptive_init_msac -- [F] float64, the
+    gain of the running winner."""
 
     def __init__(self, F, total, dev):
         i32 = dict(dtype=torch.int32, device=dev)
@@ -245,6 +247,7 @@ class AdaptiveState:
         self.R = torch.empty((F, 3, 3), dtype=torch.float64, device=dev)
         self.t = torch.empty((F, 3), dtype=torch.float64, device=dev)
         self.mask = torch.empty((total,), dtype=torch.uint8, device=dev)
+        self.best_gain = None
 
     def swap(self):
         """After compact_active: the compacted list becomes the active one."""
@@ -330,6 +333,127 @@ def compact_active(sc: Scenes, st: AdaptiveState, n_active: int):
     _chk_state(sc, st)
     A = _chk_active(sc, st.active, n_active)
     _call("ransac_adaptive", sc, "cvxpnpl_ransac_adaptive_compact", sc.F, A, _ptr(st.active), _ptr(st.done), _ptr(st.active_next), _ptr(st.n_active))
+
+
+# ---- MSAC scoring: the hypothesis of the lowest truncated quadratic cost (include/cvxpnpl_amd_ransac_msac.h) ------
+# ransac_pnp_batch(scoring="msac") selects, per scene, the hypothesis of the highest gain = sum over its inliers of (thresh^2 - r^2) /
+# thresh^2 instead of the highest inlier count: where many minimal sets explain all the inliers the count ties and the lowest index
+# decides, the gain prefers the pose that fits them best.  The kernels are those of libcvxpnpl_amd_ransac_msac.so, each next to its count
+# sibling above; sampling, the solves, the compaction, the refits and the polish are unchanged.
+
+
+def score_scenes_msac(sc: Scenes, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
+    """cvxpnpl_ransac_msac_score_scenes: (gain [F*H] float64, count [F*H] int32) of hypothesis (f, h) = (R, t)[f*H + h] over scene f.  count is
+    score_scenes' count; gain = sum over those inliers of (thresh^2 - r^2) / thresh^2, summed serially in scene order (the same bits from
+    score_active_msac and from launch to launch); an unusable hypothesis gains 0.0."""
+    _require_gpu()
+    _chk_scenes(sc)
+    H = _poses(sc, R, t, status, None, sc.F, "R must be [F*H,3,3]", min_one=False)
+    gain = torch.empty((sc.F * H,), dtype=torch.float64, device=sc.device)
+    count = torch.empty((sc.F * H,), dtype=torch.int32, device=sc.device)
+    _call("ransac_msac", sc, "cvxpnpl_ransac_msac_score_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status), _usable_mask(usable),
+          _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(gain), _ptr(count))
+    return gain, count
+
+
+def score_active_msac(sc: Scenes, active, n_active: int, R, t, thresh: float = 2.0, status=None, usable=(0, 2)):
+    """cvxpnpl_ransac_msac_score_active: (gain, count) [A*n_round] of (R, t)[a*n_round + h] over scene active[a]; the rows of
+    score_scenes_msac bit for bit.  An entry of active outside [0, F) leaves its rows unwritten."""
+    _require_gpu()
+    _chk_scenes(sc)
+    A = _chk_active(sc, active, n_active)
+    Hr = _chk_round(sc, A, R, t, status)
+    gain = torch.empty((A * Hr,), dtype=torch.float64, device=sc.device)
+    count = torch.empty((A * Hr,), dtype=torch.int32, device=sc.device)
+    _call("ransac_msac", sc, "cvxpnpl_ransac_msac_score_active", sc.F, A, _ptr(active), Hr, _ptr(sc.offsets), sc.total, _ptr(R), _ptr(t), _ptr(status),
+          _usable_mask(usable), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(gain), _ptr(count))
+    return gain, count
+
+
+def select_scenes_msac(sc: Scenes, gain, R, t, status, thresh: float = 2.0):
+    """cvxpnpl_ransac_msac_select_scenes: per scene the hypothesis of the highest gain (lowest index on an exact tie; a gain that is not > 0
+    is read as 0).  Returns what select_scenes returns -- R [F,3,3], t [F,3], head [F,4] int32 = (status, inliers, index within the scene,
+    certified hypotheses), mask [total] uint8 -- and score [F] float64, the winner's gain.  No synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    H, dev = _poses(sc, R, t, status, None, sc.F, "R must be [F*H,3,3] with H >= 1", required=False), sc.device
+    _chk(status, "status", torch.int32, (sc.F * H,), dev)
+    _chk_gain(sc, gain, sc.F * H)
+    oR = torch.empty((sc.F, 3, 3), dtype=torch.float64, device=dev)
+    ot = torch.empty((sc.F, 3), dtype=torch.float64, device=dev)
+    head = torch.empty((sc.F, 4), dtype=torch.int32, device=dev)
+    mask = torch.empty((sc.total,), dtype=torch.uint8, device=dev)
+    score = torch.empty((sc.F,), dtype=torch.float64, device=dev)
+    _call("ransac_msac", sc, "cvxpnpl_ransac_msac_select_scenes", sc.F, H, _ptr(sc.offsets), sc.total, _ptr(gain), _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K),
+          sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(oR), _ptr(ot), _ptr(head), _ptr(mask), _ptr(score))
+    return oR, ot, head, mask, score
+
+
+def adaptive_init_msac(sc: Scenes) -> AdaptiveState:
+    """adaptive_init, then cvxpnpl_ransac_msac_init: the state of an MSAC call, with best_gain [F] float64 = -1 (below every gain)."""
+    st = adaptive_init(sc)
+    st.best_gain = torch.empty((sc.F,), dtype=torch.float64, device=sc.device)
+    _call("ransac_msac", sc, "cvxpnpl_ransac_msac_init", sc.F, _ptr(st.best_gain))
+    return st
+
+
+def update_active_msac(sc: Scenes, st: AdaptiveState, n_active: int, hyp0: int, cap: int, confidence: float, gain, count, R, t, status,
+                       thresh: float = 2.0):
+    """cvxpnpl_ransac_msac_update on the first n_active entries of st.active: update_active with the gains deciding.  The round's best
+    replaces a scene's running best only by a strictly higher gain (pose, head, mask, best -- its count -- and best_gain together); the
+    stopping rule reads st.best, the inlier count of the running winner.  In place, no synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk_state_msac(sc, st)
+    conf, _ = _check_adaptive(confidence, 1)
+    A = _chk_active(sc, st.active, n_active)
+    if status is None:
+        raise ValueError("status is required")
+    Hr = _chk_round(sc, A, R, t, status, count)
+    _chk_gain(sc, gain, A * Hr)
+    h0, Hr, cp = _chk_budget(hyp0, Hr, cap)
+    _call("ransac_msac", sc, "cvxpnpl_ransac_msac_update", sc.F, A, _ptr(st.active), h0, Hr, cp, conf, _ptr(sc.offsets), sc.total, _ptr(gain), _ptr(count),
+          _ptr(R), _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+          _ptr(st.best), _ptr(st.best_gain), _ptr(st.mask), _ptr(st.hyp_used), _ptr(st.done))
+
+
+def msac_gain_host(scene_2d, scene_3d, sizes, K, R, t, thresh: float = 2.0, status=None, usable=(0, 2), n_threads: int = 0):
+    """cvxpnpl_ransac_msac_score_host: what score_scenes_msac computes, on host arrays by the functions the kernels call.  scene_2d [sum M,2],
+    scene_3d [sum M,3] packed with sizes (F ints), K [3,3] or [F,3,3], R [F*H,3,3], t [F*H,3], status [F*H] or None.  Returns numpy
+    (gain [F*H] float64, count [F*H] int32).  No GPU needed."""
+    import ctypes as C
+
+    szs = [int(m) for m in sizes]
+    F, total = len(szs), sum(szs)
+    if F < 1 or any(m < 0 for m in szs):
+        raise ValueError("sizes: at least one scene, no negative size")
+    x = _np.ascontiguousarray(scene_2d, dtype=_np.float64)
+    X = _np.ascontiguousarray(scene_3d, dtype=_np.float64)
+    Kh = _np.ascontiguousarray(K, dtype=_np.float64)
+    Rh = _np.ascontiguousarray(R, dtype=_np.float64)
+    th = _np.ascontiguousarray(t, dtype=_np.float64)
+    if x.shape != (total, 2) or X.shape != (total, 3):
+        raise ValueError(f"packed scenes: expected [{total},2] and [{total},3], got {x.shape} and {X.shape}")
+    if Kh.shape != (3, 3) and Kh.shape != (F, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{F},3,3], got {Kh.shape}")
+    if Rh.ndim != 3 or Rh.shape[1:] != (3, 3) or Rh.shape[0] % F or th.shape != (Rh.shape[0], 3):
+        raise ValueError(f"R must be [F*H,3,3] and t [F*H,3], got {Rh.shape} and {th.shape}")
+    n = Rh.shape[0]
+    st = None
+    if status is not None:
+        st = _np.ascontiguousarray(status, dtype=_np.int32)
+        if st.shape != (n,):
+            raise ValueError(f"status: shape {st.shape}, expected ({n},)")
+    off = _np.zeros(F + 1, dtype=_np.int64)
+    _np.cumsum(szs, out=off[1:])
+    gain, count = _np.zeros(n, dtype=_np.float64), _np.zeros(n, dtype=_np.int32)
+    L = _lib.ransac_msac_lib()
+    ptr = lambda a: None if a is None else C.c_void_p(a.ctypes.data)  # noqa: E731
+    rc = L.cvxpnpl_ransac_msac_score_host(F, n // F, ptr(off), total, ptr(Rh), ptr(th), ptr(st), _usable_mask(usable), ptr(Kh), int(Kh.ndim == 3),
+                                          ptr(x), ptr(X), float(thresh), ptr(gain), ptr(count), int(n_threads))
+    if rc != 0:
+        raise RuntimeError(f"cvxpnpl_ransac_msac_score_host failed ({rc}): {L.cvxpnpl_ransac_msac_last_error().decode()}")
+    return gain, count
 
 
 # ---- guided sampling: the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h, DESIGN.md section 20) ----------------
@@ -504,7 +628,7 @@ def _finish(sc, kind, R, t, head, masks, thresh, refit, refit_rounds, polish, n_
 
 def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
                      refit_rounds: int = 1, sizes=None, device=None, polish: bool = False, confidence: Optional[float] = None, round_hyp: int = 64,
-                     quality=None, pool_full: Optional[int] = None, **solver_opts):
+                     quality=None, pool_full: Optional[int] = None, scoring: str = "count", **solver_opts):
     """Robust PnP for F scenes of different sizes in one launch sequence (what ransac_pnp does for one scene per call).
 
     Scenes: lists of F arrays pts_2d[f] [M_f,2] / pts_3d[f] [M_f,3], or packed [sum M,2] / [sum M,3] with `sizes` (a host sequence of F
@@ -525,10 +649,21 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     [M_f], or packed [sum M] with `sizes`; any real dtype.  Every scene is ranked once (rank_scenes) and hypothesis h draws its minimal
     set from the pool_size(h, M_f, pool_full) best-ranked correspondences: 4 at h = 0, growing with h, the whole scene from h = pool_full
     on, where the draws are the uniform ones again.  pool_full (an int >= 0) defaults to n_hyp; 0 is the uniform sampler.  With
-    confidence the stopping rule is unchanged and counts inliers of the whole scene.  The result gains pool_full."""
+    confidence the stopping rule is unchanged and counts inliers of the whole scene.  The result gains pool_full.
+    scoring ("count": the code above unchanged; "msac"): what selects a scene's hypothesis among its draws.  "msac" takes the highest
+    gain = sum over the hypothesis' inliers of (thresh^2 - r^2) / thresh^2, i.e. the lowest truncated quadratic cost sum min(r^2, thresh^2),
+    the lowest index winning an exact tie -- where many minimal sets explain all the inliers, the count ties and the gain prefers the
+    pose that fits them best (score_scenes_msac, select_scenes_msac; with confidence, score_active_msac and update_active_msac, a scene
+    stopping on the inlier count of its running MSAC winner).  quality / pool_full compose unchanged: they only change the draws.  The
+    result of an "msac" call gains "score" ([F] float64 on the device: the gain of the selected minimal hypothesis) and "scoring"; the
+    result of a "count" call is today's, key for key.  Refits and polish keep
+    their acceptance rule (at least the consensus count) and their kernels; after a refit is taken, score still describes the
+    hypothesis that was selected.  Out of scope: ransac_pnp (one scene, kernels of the solver library), the point-and-line calls, and a
+    gain-based refit rule."""
     szs = _check_scenes(pts_2d, pts_3d, K, sizes)
     seeds, conf, round_hyp = _batch_head(len(szs), seed, n_hyp, confidence, round_hyp)
     pool_full = _check_quality(quality, pool_full, szs, sizes is not None, n_hyp)
+    msac = _chk_scoring(scoring) == "msac"  # (after every earlier check: the order of their errors is pinned)
     sc = pack_scenes(pts_2d, pts_3d, K, sizes=szs if sizes is not None else None, device=device, seeds=seeds)
     guided = None
     if quality is not None:  # the ranking: once per call, before the launch sequence
@@ -539,22 +674,35 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     def solve(p2, p3, Kh):  # the minimal solves of a fixed budget or of a round, in one launch sequence of the solver library
         return pnp_batch(p2, p3, Kh if sc.per_scene_K else sc.K, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
 
-    adaptive = None
+    adaptive = score = None
     if conf is not None:
         cap = int(n_hyp)
         if guided is None:
             stage = lambda act, A, h0, Hr: solve(*sample_active(sc, act, A, h0, Hr, cap))  # noqa: E731
         else:
             stage = lambda act, A, h0, Hr: solve(*sample_active_guided(sc, act, A, h0, Hr, cap, *guided))  # noqa: E731
-        state = adaptive_init(sc)
-        adaptive = (state, _rounds(sc, state, (stage, score_active, update_active), cap, conf, round_hyp, thresh), conf)
+        if msac:  # the rounds with the msac stages: the round's (gain, count) travel from the score stage to the update stage as one
+            state = adaptive_init_msac(sc)
+            update = lambda sc_, st, A, h0, cp, cf, gc, R_, t_, s, th: update_active_msac(sc_, st, A, h0, cp, cf, gc[0], gc[1], R_, t_, s, th)  # noqa: E731
+            adaptive = (state, _rounds(sc, state, (stage, score_active_msac, update), cap, conf, round_hyp, thresh), conf)
+            score = state.best_gain
+        else:
+            state = adaptive_init(sc)
+            adaptive = (state, _rounds(sc, state, (stage, score_active, update_active), cap, conf, round_hyp, thresh), conf)
         R, t, head, mask = state.R, state.t, state.head, state.mask
+    elif msac:  # no torch kernel from here to the read-back
+        res = solve(*(sample_scenes(sc, n_hyp) if guided is None else sample_scenes_guided(sc, n_hyp, *guided)))
+        gain, _ = score_scenes_msac(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
+        R, t, head, mask, score = select_scenes_msac(sc, gain, res.R, res.t, res.status, thresh)
     else:  # no torch kernel from here to the read-back
         res = solve(*(sample_scenes(sc, n_hyp) if guided is None else sample_scenes_guided(sc, n_hyp, *guided)))
         count = score_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
         R, t, head, mask = select_scenes(sc, count, res.R, res.t, res.status, thresh)
-    return _finish(sc, (assemble_consensus, refit_update_scenes, (("inliers", "offsets"),)), R, t, head, (mask,), thresh, refit, refit_rounds,
-                   polish, n_hyp, adaptive, pool_full)
+    out = _finish(sc, (assemble_consensus, refit_update_scenes, (("inliers", "offsets"),)), R, t, head, (mask,), thresh, refit, refit_rounds,
+                  polish, n_hyp, adaptive, pool_full)
+    if msac:  # (the count call's result keeps exactly its keys)
+        out["scoring"], out["score"] = scoring, score
+    return out
 
 
 # ---- points AND lines, many scenes (include/cvxpnpl_amd_ransac_pnpl.h) --------------------------------------------
