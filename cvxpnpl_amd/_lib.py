@@ -395,6 +395,25 @@ def ransac_msac_lib():
     return _load(RANSAC_MSAC_LIB_PATH, RANSAC_MSAC_EXPORTS, _ransac_msac_argtypes)
 
 
+# local optimisation in adaptive RANSAC (include/cvxpnpl_amd_ransac_lo.h): the fourteenth library
+RANSAC_LO_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_lo.so")
+RANSAC_LO_EXPORTS = ("cvxpnpl_ransac_lo_init", "cvxpnpl_ransac_lo_assemble", "cvxpnpl_ransac_lo_update", "cvxpnpl_ransac_lo_assemble_host",
+                     "cvxpnpl_ransac_lo_last_error")
+
+
+def _ransac_lo_argtypes(L):
+    p, i32, i64, f64 = C.c_void_p, C.c_int32, C.c_int64, C.c_double
+    L.cvxpnpl_ransac_lo_init.argtypes = [i64, p, p]
+    L.cvxpnpl_ransac_lo_assemble.argtypes = [i64, i64, p, p, i64, p, p, p, p, p, i32, f64, p, p, p, p]
+    L.cvxpnpl_ransac_lo_update.argtypes = [i64, i64, p, i32, f64, p, i64, p, p, p, p, p, i32, p, p, f64, p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_lo_assemble_host.argtypes = [i64, i64, p, p, i64, p, p, p, p, p, i32, f64, p, p, p, i32]
+
+
+def ransac_lo_lib():
+    """Load libcvxpnpl_amd_ransac_lo.so (loudly)."""
+    return _load(RANSAC_LO_LIB_PATH, RANSAC_LO_EXPORTS, _ransac_lo_argtypes)
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

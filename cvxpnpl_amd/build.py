@@ -17,7 +17,7 @@ DEPS = [SRC, HOST_SRC, LANE_SRC, *SOLVER_ENTRY_HEADERS, os.path.join(HERE, "csrc
         os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd.h")]
 
 
-RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the six RANSAC entry files share
+RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the seven RANSAC entry files share
 
 
 def hipcc():
@@ -226,6 +226,22 @@ def ransac_msac_command(out=RANSAC_MSAC_OUT):
     return ransac_compile_cmd(out)[:-1] + [RANSAC_MSAC_SRC]
 
 
+# local optimisation in adaptive RANSAC, the running best refitted every round (include/cvxpnpl_amd_ransac_lo.h): the fourteenth library,
+# the flags of the third.  (Named as the thirteenth pair is, apart from the twelve tests/test_build_deps.py pins;
+# tests/test_ransac_lo_library.py holds this list against the include closure of its source.)
+RANSAC_LO_SRC = os.path.join(HERE, "csrc", "ransac_lo_hip.hip")
+RANSAC_LO_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_lo.so")
+RANSAC_LO_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_lo.resources.txt")
+RANSAC_LO_SOURCES = [RANSAC_LO_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_lo_kernel.h"), os.path.join(HERE, "csrc", "ransac_lo_core.h"),
+                     os.path.join(HERE, "csrc", "ransac_adaptive_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+                     os.path.join(HERE, "csrc", "host_pool.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_lo.h")]
+
+
+def ransac_lo_command(out=RANSAC_LO_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_LO_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -292,8 +308,12 @@ def build_ransac_msac(force=False, verbose=False):
     return _build_one(RANSAC_MSAC_OUT, RANSAC_MSAC_RESOURCES, RANSAC_MSAC_SOURCES, ransac_msac_command(), force, verbose)
 
 
+def build_ransac_lo(force=False, verbose=False):
+    return _build_one(RANSAC_LO_OUT, RANSAC_LO_RESOURCES, RANSAC_LO_SOURCES, ransac_lo_command(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All thirteen libraries; returns the solver's (OUT)."""
+    """All fourteen libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -307,6 +327,7 @@ def build(force=False, verbose=False):
     build_ransac_pnpl_adaptive(force, verbose)
     build_refine_robust_auto(force, verbose)
     build_ransac_msac(force, verbose)
+    build_ransac_lo(force, verbose)
     return OUT
 
 

@@ -1,5 +1,5 @@
-// ransac_entry.h -- what the entry points of the six RANSAC libraries (ransac, ransac_pnpl, ransac_adaptive, ransac_guided,
-// ransac_pnpl_adaptive, ransac_msac) share around their kernels: the error text, the argument contract of a scenes call and of a round, and the launch
+// ransac_entry.h -- what the entry points of the seven RANSAC libraries (ransac, ransac_pnpl, ransac_adaptive, ransac_guided,
+// ransac_pnpl_adaptive, ransac_msac, ransac_lo) share around their kernels: the error text, the argument contract of a scenes call and of a round, and the launch
 // of a kernel whose grid is (hypotheses, scenes or active entries).  Host-only.  Every function is inline and hidden: each library keeps
 // a copy of its own -- its own thread-local message -- and exports nothing of this.
 //

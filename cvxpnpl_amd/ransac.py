@@ -238,7 +238,7 @@ class AdaptiveState:
     """What an adaptive call keeps over its rounds, on the scenes' device: active, active_next [F] int32 (the first n entries count),
     n_active [1] int32, done [F] int32, R [F,3,3], t [F,3], head [F,4] int32, best [F] int32 (the count of the running winner), mask
     [total] uint8, hyp_used [F] int32.  Built by adaptive_init.  best_gain: None, or -- an MSAC call, adaptive_init_msac -- [F] float64, the
-    gain of the running winner."""
+    gain of the running winner.  lo_taken: None, or -- a call with local optimisation, lo_init -- [F] int32, the refits taken per scene."""
 
     def __init__(self, F, total, dev):
         i32 = dict(dtype=torch.int32, device=dev)
@@ -248,6 +248,7 @@ class AdaptiveState:
         self.t = torch.empty((F, 3), dtype=torch.float64, device=dev)
         self.mask = torch.empty((total,), dtype=torch.uint8, device=dev)
         self.best_gain = None
+        self.lo_taken = None
 
     def swap(self):
         """After compact_active: the compacted list becomes the active one."""
@@ -456,6 +457,136 @@ def msac_gain_host(scene_2d, scene_3d, sizes, K, R, t, thresh: float = 2.0, stat
     return gain, count
 
 
+# ---- local optimisation: the running best refitted every round (include/cvxpnpl_amd_ransac_lo.h) -----------------
+# ransac_pnp_batch(confidence=..., local_opt=n) ends every round with n LO steps over the scenes still active: the correspondences that
+# pass the inlier predicate at a scene's running pose are assembled into a cost (lo_assemble_active), all entries' costs are solved at the
+# cost seam (solve_cost_batch), and a refitted pose that is usable and counts at least the running best is taken (lo_update_active) -- so
+# the stopping rule reads the inlier share a non-minimal fit explains, not a four-point pose's.  The kernels are those of
+# libcvxpnpl_amd_ransac_lo.so; the draws, the minimal solves, the round's own update and the compaction are unchanged.
+
+
+def lo_thresholds(thresh: float, local_opt: int, lo_widen: float = 1.0):
+    """The assembly thresholds thresh * m_k of the local_opt steps of a round, in float64 on the host:
+    m_k = 1 + (lo_widen - 1) (n - 1 - k) / max(n - 1, 1) -- lo_widen * thresh in the first step, thresh in the last (and for n = 1)."""
+    n, w, th = int(local_opt), float(lo_widen), float(thresh)
+    return [th * (1.0 + (w - 1.0) * (n - 1 - k) / max(n - 1, 1)) for k in range(n)]
+
+
+def _check_local_opt(local_opt, lo_widen, confidence, scoring):
+    """Host-side validation of the LO keywords (nothing here needs a GPU).  Returns (local_opt, lo_widen)."""
+    if isinstance(local_opt, bool) or not isinstance(local_opt, (int, _np.integer)) or int(local_opt) < 0:
+        raise ValueError(f"local_opt must be an int >= 0, got {local_opt!r}")
+    try:
+        w = float(lo_widen)
+    except (TypeError, ValueError):
+        raise ValueError(f"lo_widen must be a finite number >= 1, got {lo_widen!r}") from None
+    if not (1.0 <= w < float("inf")):  # (NaN compares false)
+        raise ValueError(f"lo_widen must be a finite number >= 1, got {lo_widen!r}")
+    n = int(local_opt)
+    if n > 0 and confidence is None:
+        raise ValueError("local_opt needs confidence=...: it refits the running best of an adaptive call (the fixed budget's LO step is refit=)")
+    if n > 0 and scoring == "msac":
+        raise ValueError("local_opt with scoring='msac' is not supported: a gain-based acceptance rule for refits is out of scope")
+    return n, w
+
+
+def lo_init(sc: Scenes, st: AdaptiveState) -> AdaptiveState:
+    """cvxpnpl_ransac_lo_init: st.lo_taken [F] int32 = 0, the refits taken per scene.  Returns st."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk_state(sc, st)
+    st.lo_taken = torch.empty((sc.F,), dtype=torch.int32, device=sc.device)
+    _call("ransac_lo", sc, "cvxpnpl_ransac_lo_init", sc.F, _ptr(st.lo_taken))
+    return st
+
+
+def lo_assemble_active(sc: Scenes, st: AdaptiveState, n_active: int, thresh_k: float, out=None):
+    """cvxpnpl_ransac_lo_assemble on the first n_active entries of st.active: (B27 [A,27], Q45 [A,45], cnt [A] int32) of the correspondences
+    of scene st.active[a] that pass the inlier predicate at its running pose st.R[f], st.t[f] under thresh_k (the step's thresh * m_k,
+    lo_thresholds); feed solve_cost_batch.  No mask is read or written; the sums meet in a fixed order.  Fewer than three taken: NaN, with
+    the count reported.  An entry outside [0, F) leaves its rows unwritten.  out: None, or the three tensors to write into.  No
+    synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk_state(sc, st)
+    A, dev = _chk_active(sc, st.active, n_active), sc.device
+    if out is None:
+        out = (torch.empty((A, 27), dtype=torch.float64, device=dev), torch.empty((A, 45), dtype=torch.float64, device=dev),
+               torch.empty((A,), dtype=torch.int32, device=dev))
+    Bt, Qt, cnt = out
+    _chk(Bt, "out B27", torch.float64, (A, 27), dev)
+    _chk(Qt, "out Q45", torch.float64, (A, 45), dev)
+    _chk(cnt, "out cnt", torch.int32, (A,), dev)
+    _call("ransac_lo", sc, "cvxpnpl_ransac_lo_assemble", sc.F, A, _ptr(st.active), _ptr(sc.offsets), sc.total, _ptr(sc.x), _ptr(sc.X), _ptr(st.R), _ptr(st.t),
+          _ptr(sc.K), sc.per_scene_K, float(thresh_k), _ptr(Bt), _ptr(Qt), _ptr(cnt))
+    return Bt, Qt, cnt
+
+
+def lo_update_active(sc: Scenes, st: AdaptiveState, n_active: int, cap: int, confidence: float, fit, cnt, thresh: float = 2.0):
+    """cvxpnpl_ransac_lo_update on the first n_active entries of st.active: the refit fit.R[a], fit.t[a], fit.status[a] of the cnt[a]
+    correspondences lo_assemble_active took is counted at thresh and TAKEN when its status is 0 or 2, cnt[a] >= 4 and its count is at least
+    max(st.best[f], st.head[f,1]) -- the non-minimal fit wins a tie.  Then pose, head[f,0:2], best[f] and the scene's slice of the mask
+    change together, head[f,2] keeps the index of the hypothesis that seeded it and st.lo_taken[f] goes up by one.  Taken or not,
+    st.done[a] |= the stopping rule at st.hyp_used[f], st.best[f].  In place, no synchronisation."""
+    _require_gpu()
+    _chk_scenes(sc)
+    _chk_state(sc, st)
+    if getattr(st, "lo_taken", None) is None:
+        raise ValueError("state.lo_taken is missing: the state of a call with local optimisation goes through lo_init")
+    dev = sc.device
+    _chk(st.lo_taken, "state.lo_taken", torch.int32, (sc.F,), dev)
+    conf, _ = _check_adaptive(confidence, 1)
+    A = _chk_active(sc, st.active, n_active)
+    cp = int(cap)
+    if not 0 <= cp <= 0x7FFFFFFF:
+        raise ValueError(f"cap must be an int >= 0 (and below 2^31), got {cap!r}")
+    _chk(fit.R, "fit.R", torch.float64, (A, 3, 3), dev)
+    _chk(fit.t, "fit.t", torch.float64, (A, 3), dev)
+    _chk(fit.status, "fit.status", torch.int32, (A,), dev)
+    _chk(cnt, "cnt", torch.int32, (A,), dev)
+    _call("ransac_lo", sc, "cvxpnpl_ransac_lo_update", sc.F, A, _ptr(st.active), cp, conf, _ptr(sc.offsets), sc.total, _ptr(fit.R), _ptr(fit.t),
+          _ptr(fit.status), _ptr(cnt), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+          _ptr(st.best), _ptr(st.mask), _ptr(st.hyp_used), _ptr(st.lo_taken), _ptr(st.done))
+
+
+def lo_assemble_host(scene_2d, scene_3d, sizes, K, R, t, active, thresh_k: float, n_threads: int = 0):
+    """cvxpnpl_ransac_lo_assemble_host: what lo_assemble_active computes, on host arrays by the rules the kernel follows (the same lanes,
+    the same order of the sums).  scene_2d [sum M,2], scene_3d [sum M,3] packed with sizes (F ints), K [3,3] or [F,3,3], R [F,3,3], t [F,3]
+    the running poses, active: A scene indices.  Returns numpy (B27 [A,27], Q45 [A,45], cnt [A] int32); the rows of an entry outside
+    [0, F) keep their initial NaN / -1.  No GPU needed."""
+    import ctypes as C
+
+    szs = [int(m) for m in sizes]
+    F, total = len(szs), sum(szs)
+    if F < 1 or any(m < 0 for m in szs):
+        raise ValueError("sizes: at least one scene, no negative size")
+    x = _np.ascontiguousarray(scene_2d, dtype=_np.float64)
+    X = _np.ascontiguousarray(scene_3d, dtype=_np.float64)
+    Kh = _np.ascontiguousarray(K, dtype=_np.float64)
+    Rh = _np.ascontiguousarray(R, dtype=_np.float64)
+    th = _np.ascontiguousarray(t, dtype=_np.float64)
+    act = _np.ascontiguousarray(active, dtype=_np.int32)
+    if x.shape != (total, 2) or X.shape != (total, 3):
+        raise ValueError(f"packed scenes: expected [{total},2] and [{total},3], got {x.shape} and {X.shape}")
+    if Kh.shape != (3, 3) and Kh.shape != (F, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{F},3,3], got {Kh.shape}")
+    if Rh.shape != (F, 3, 3) or th.shape != (F, 3):
+        raise ValueError(f"R must be [{F},3,3] and t [{F},3], got {Rh.shape} and {th.shape}")
+    if act.ndim != 1:
+        raise ValueError(f"active must have one dimension, got shape {act.shape}")
+    A = act.shape[0]
+    off = _np.zeros(F + 1, dtype=_np.int64)
+    _np.cumsum(szs, out=off[1:])
+    Bt, Qt, cnt = _np.full((A, 27), _np.nan), _np.full((A, 45), _np.nan), _np.full(A, -1, dtype=_np.int32)
+    L = _lib.ransac_lo_lib()
+    ptr = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)  # noqa: E731
+    rc = L.cvxpnpl_ransac_lo_assemble_host(F, A, ptr(act), ptr(off), total, ptr(x), ptr(X), ptr(Rh), ptr(th), ptr(Kh), int(Kh.ndim == 3), float(thresh_k),
+                                           ptr(Bt), ptr(Qt), ptr(cnt), int(n_threads))
+    if rc != 0:
+        raise RuntimeError(f"cvxpnpl_ransac_lo_assemble_host failed ({rc}): {L.cvxpnpl_ransac_lo_last_error().decode()}")
+    return Bt, Qt, cnt
+
+
 # ---- guided sampling: the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h, DESIGN.md section 20) ----------------
 # ransac_pnp_batch(quality=...) ranks every scene's correspondences by a matcher's score once per call and draws hypothesis h from the
 # n(h) best of them; the pool grows with h (the growth function of PROSAC) and is the whole scene from h = pool_full on, where the draw is
@@ -557,11 +688,12 @@ def _batch_head(F, seed, n_hyp, confidence, round_hyp):
     return seeds, conf, round_hyp
 
 
-def _rounds(sc, st, stages, cap, conf, round_hyp, thresh):
+def _rounds(sc, st, stages, cap, conf, round_hyp, thresh, after_update=None):
     """The rounds of a batch call with confidence=... over the state st (adaptive_init / adaptive_pnpl_init): returns their number.
     stages: what differs between the scene kinds -- solve(active, n_active, hyp0, n_round), which draws the round's minimal sets and
     solves them, and the kind's score_*_active and update_*_active.  One 4-byte read-back per round -- the number of scenes still active,
-    which the next round's solve needs as a host number (its batch size)."""
+    which the next round's solve needs as a host number (its batch size).  after_update(n_active), optional, runs between the round's
+    update and its compaction, over the same active list: it may change the state and set st.done."""
     solve, score, update = stages
     A, h0, rounds = sc.F, 0, 0
     while A > 0 and h0 < cap:
@@ -569,6 +701,8 @@ def _rounds(sc, st, stages, cap, conf, round_hyp, thresh):
         res = solve(st.active, A, h0, Hr)
         count = score(sc, st.active, A, res.R, res.t, thresh, status=res.status, usable=(0, 2))
         update(sc, st, A, h0, cap, conf, count, res.R, res.t, res.status, thresh)
+        if after_update is not None:
+            after_update(A)
         compact_active(sc, st, A)
         A = int(st.n_active.cpu()[0])   # the round's one synchronisation
         st.swap()
@@ -628,7 +762,8 @@ def _finish(sc, kind, R, t, head, masks, thresh, refit, refit_rounds, polish, n_
 
 def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0, refit: bool = True,
                      refit_rounds: int = 1, sizes=None, device=None, polish: bool = False, confidence: Optional[float] = None, round_hyp: int = 64,
-                     quality=None, pool_full: Optional[int] = None, scoring: str = "count", **solver_opts):
+                     quality=None, pool_full: Optional[int] = None, scoring: str = "count", local_opt: int = 0, lo_widen: float = 1.0,
+                     **solver_opts):
     """Robust PnP for F scenes of different sizes in one launch sequence (what ransac_pnp does for one scene per call).
 
     Scenes: lists of F arrays pts_2d[f] [M_f,2] / pts_3d[f] [M_f,3], or packed [sum M,2] / [sum M,3] with `sizes` (a host sequence of F
@@ -659,11 +794,21 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
     result of a "count" call is today's, key for key.  Refits and polish keep
     their acceptance rule (at least the consensus count) and their kernels; after a refit is taken, score still describes the
     hypothesis that was selected.  Out of scope: ransac_pnp (one scene, kernels of the solver library), the point-and-line calls, and a
-    gain-based refit rule."""
+    gain-based refit rule.
+    local_opt (an int >= 0; 0: the code above unchanged, and today's result key for key; needs confidence, scoring="count"): LO-RANSAC.
+    Every round ends with local_opt steps over the scenes still active: the correspondences within thresh * m_k of a scene's running
+    pose are assembled into a cost (lo_assemble_active), the costs are solved at the cost seam with this call's eps / max_iters /
+    solver options, and a refit of status 0 or 2, fitted to at least four correspondences, that counts -- at thresh -- at least the
+    running best replaces it, a tie going to the fit (lo_update_active); the stopping rule then reads that count.  m_k falls from
+    lo_widen (a float >= 1) in the first step to 1 in the last (lo_thresholds).  The draws do not depend on it, and a later round's
+    minimal hypothesis replaces the running best only by a strictly higher count, so no scene draws more than without it.  Every active
+    scene is refitted every round, changed or not.  The result gains lo_taken [F] (host int32: refits taken per scene), local_opt and
+    lo_widen; best_index stays the index of the minimal hypothesis that seeded the running pose."""
     szs = _check_scenes(pts_2d, pts_3d, K, sizes)
     seeds, conf, round_hyp = _batch_head(len(szs), seed, n_hyp, confidence, round_hyp)
     pool_full = _check_quality(quality, pool_full, szs, sizes is not None, n_hyp)
     msac = _chk_scoring(scoring) == "msac"  # (after every earlier check: the order of their errors is pinned)
+    local_opt, lo_widen = _check_local_opt(local_opt, lo_widen, confidence, scoring)
     sc = pack_scenes(pts_2d, pts_3d, K, sizes=szs if sizes is not None else None, device=device, seeds=seeds)
     guided = None
     if quality is not None:  # the ranking: once per call, before the launch sequence
@@ -686,6 +831,17 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
             update = lambda sc_, st, A, h0, cp, cf, gc, R_, t_, s, th: update_active_msac(sc_, st, A, h0, cp, cf, gc[0], gc[1], R_, t_, s, th)  # noqa: E731
             adaptive = (state, _rounds(sc, state, (stage, score_active_msac, update), cap, conf, round_hyp, thresh), conf)
             score = state.best_gain
+        elif local_opt:  # the rounds as below, each ending in local_opt refits of the running bests
+            state = lo_init(sc, adaptive_init(sc))
+            steps = lo_thresholds(thresh, local_opt, lo_widen)
+
+            def lo_steps(A):
+                for thresh_k in steps:
+                    Bt, Qt, cnt = lo_assemble_active(sc, state, A, thresh_k)
+                    fit = solve_cost_batch(Qt, Bt, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+                    lo_update_active(sc, state, A, cap, conf, fit, cnt, thresh)
+
+            adaptive = (state, _rounds(sc, state, (stage, score_active, update_active), cap, conf, round_hyp, thresh, after_update=lo_steps), conf)
         else:
             state = adaptive_init(sc)
             adaptive = (state, _rounds(sc, state, (stage, score_active, update_active), cap, conf, round_hyp, thresh), conf)
@@ -702,6 +858,8 @@ def ransac_pnp_batch(pts_2d, pts_3d, K, n_hyp: int = 1024, thresh: float = 2.0, 
                   polish, n_hyp, adaptive, pool_full)
     if msac:  # (the count call's result keeps exactly its keys)
         out["scoring"], out["score"] = scoring, score
+    if local_opt:  # (and the call without local optimisation exactly its own)
+        out.update(lo_taken=state.lo_taken.cpu(), local_opt=local_opt, lo_widen=lo_widen)
     return out
 
 
