@@ -20,3 +20,4 @@ from .ransac import ransac_pnl, ransac_pnl_batch, ransac_pnp_batch, ransac_pnpl,
 from .ransac import (adaptive_init_msac, msac_gain_host, score_active_msac, score_scenes_msac, select_scenes_msac,  # noqa: F401
                      update_active_msac)
 from .ransac import lo_assemble_active, lo_assemble_host, lo_init, lo_thresholds, lo_update_active  # noqa: F401
+from .ransac import lo_assemble_pnpl_active, lo_assemble_pnpl_host, lo_update_pnpl_active  # noqa: F401

@@ -414,6 +414,25 @@ def ransac_lo_lib():
     return _load(RANSAC_LO_LIB_PATH, RANSAC_LO_EXPORTS, _ransac_lo_argtypes)
 
 
+# local optimisation in adaptive RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl_lo.h): the fifteenth library
+RANSAC_PNPL_LO_LIB_PATH = os.path.join(_HERE, "libcvxpnpl_amd_ransac_pnpl_lo.so")
+RANSAC_PNPL_LO_EXPORTS = ("cvxpnpl_ransac_pnpl_lo_assemble", "cvxpnpl_ransac_pnpl_lo_update", "cvxpnpl_ransac_pnpl_lo_assemble_host",
+                          "cvxpnpl_ransac_pnpl_lo_last_error")
+
+
+def _ransac_pnpl_lo_argtypes(L):
+    i64, i32, f64, p = C.c_int64, C.c_int32, C.c_double, C.c_void_p
+    scenes, data = [p, i64, p, i64], [p, p, p, p]  # d_pt_offsets, n_pts, d_ln_offsets, n_lines; d_pts_2d, d_pts_3d, d_line_2d, d_line_3d
+    L.cvxpnpl_ransac_pnpl_lo_assemble.argtypes = [i64, i64, p] + scenes + data + [p, p, p, i32, f64, p, p, p, p]
+    L.cvxpnpl_ransac_pnpl_lo_update.argtypes = [i64, i64, p, i32, f64] + scenes + [p, p, p, p, p, i32] + data + [f64, p, p, p, p, p, p, p, p, p, p]
+    L.cvxpnpl_ransac_pnpl_lo_assemble_host.argtypes = [i64, i64, p] + scenes + data + [p, p, p, i32, f64, p, p, p, i32]
+
+
+def ransac_pnpl_lo_lib():
+    """Load libcvxpnpl_amd_ransac_pnpl_lo.so (loudly)."""
+    return _load(RANSAC_PNPL_LO_LIB_PATH, RANSAC_PNPL_LO_EXPORTS, _ransac_pnpl_lo_argtypes)
+
+
 def default_opts(**overrides):
     o = Opts()
     lib().cvxpnpl_default_opts(C.byref(o))

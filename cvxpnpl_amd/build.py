@@ -242,6 +242,24 @@ def ransac_lo_command(out=RANSAC_LO_OUT):
     return ransac_compile_cmd(out)[:-1] + [RANSAC_LO_SRC]
 
 
+# local optimisation in adaptive RANSAC over points and lines (include/cvxpnpl_amd_ransac_pnpl_lo.h): the fifteenth library, the flags of the
+# third.  (Named as the thirteenth and fourteenth pairs are; tests/test_ransac_pnpl_lo_library.py holds this list against the include
+# closure of its source.)
+RANSAC_PNPL_LO_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_lo_hip.hip")
+RANSAC_PNPL_LO_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_lo.so")
+RANSAC_PNPL_LO_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_lo.resources.txt")
+RANSAC_PNPL_LO_SOURCES = [RANSAC_PNPL_LO_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_pnpl_lo_kernel.h"),
+                          os.path.join(HERE, "csrc", "ransac_pnpl_lo_core.h"), os.path.join(HERE, "csrc", "ransac_lo_core.h"),
+                          os.path.join(HERE, "csrc", "ransac_pnpl_common.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
+                          os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"),
+                          os.path.join(HERE, "csrc", "problem_io.h"), os.path.join(HERE, "csrc", "host_pool.h"),
+                          os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_pnpl_lo.h")]
+
+
+def ransac_pnpl_lo_command(out=RANSAC_PNPL_LO_OUT):
+    return ransac_compile_cmd(out)[:-1] + [RANSAC_PNPL_LO_SRC]
+
+
 def _build_one(out, resources, deps, cmd, force, verbose):
     deps = [d for d in deps if os.path.exists(d)]
     fresh = os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(d) for d in deps)
@@ -312,8 +330,12 @@ def build_ransac_lo(force=False, verbose=False):
     return _build_one(RANSAC_LO_OUT, RANSAC_LO_RESOURCES, RANSAC_LO_SOURCES, ransac_lo_command(), force, verbose)
 
 
+def build_ransac_pnpl_lo(force=False, verbose=False):
+    return _build_one(RANSAC_PNPL_LO_OUT, RANSAC_PNPL_LO_RESOURCES, RANSAC_PNPL_LO_SOURCES, ransac_pnpl_lo_command(), force, verbose)
+
+
 def build(force=False, verbose=False):
-    """All fourteen libraries; returns the solver's (OUT)."""
+    """All fifteen libraries; returns the solver's (OUT)."""
     _build_one(OUT, RESOURCES, DEPS, compile_cmd(), force, verbose)
     build_grad(force, verbose)
     build_ransac(force, verbose)
@@ -328,6 +350,7 @@ def build(force=False, verbose=False):
     build_refine_robust_auto(force, verbose)
     build_ransac_msac(force, verbose)
     build_ransac_lo(force, verbose)
+    build_ransac_pnpl_lo(force, verbose)
     return OUT
 
 

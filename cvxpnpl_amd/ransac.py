@@ -1183,6 +1183,112 @@ def update_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, hyp0: i
           _ptr(t), _ptr(status), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
           _ptr(st.best), _ptr(st.mask), _ptr(st.mask_lines), _ptr(st.hyp_used), _ptr(st.done))
 
+# ---- local optimisation for points AND lines (include/cvxpnpl_amd_ransac_pnpl_lo.h) -------------------------------
+# ransac_pnpl_batch(confidence=..., local_opt=n): the LO steps of section 24 over the union of a scene's points and lines.  The state is
+# adaptive_pnpl_init's plus lo_init's counter (the fourteenth library's kernel, which reads nothing of a scene); the two kernels that
+# touch points and lines are those of libcvxpnpl_amd_ransac_pnpl_lo.so.
+
+
+def _chk_pnpl_lo_state(sc, st):
+    _chk_state(sc, st)
+    _chk(getattr(st, "mask_lines", None), "state.mask_lines", torch.uint8, (sc.line_total,), sc.device)
+
+
+def lo_assemble_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, thresh_k: float, out=None):
+    """cvxpnpl_ransac_pnpl_lo_assemble on the first n_active entries of st.active: (B27 [A,27], Q45 [A,45], cnt [A] int32) of the points
+    of scene st.active[a] that pass the point predicate and of its lines that pass the line predicate -- both end points in front of the
+    camera and within thresh_k pixels of the image line -- at the running pose st.R[f], st.t[f] under thresh_k (the step's
+    thresh * m_k, lo_thresholds); cnt counts points plus lines, a line once; feed solve_cost_batch.  No mask is read or written; the sums
+    meet in a fixed order (a lane's points, then its lines) about the centre of the first three taken 3D records, points first.  Fewer
+    than three taken: NaN, with the count reported.  An entry outside [0, F) leaves its rows unwritten.  out: None, or the three tensors
+    to write into.  No synchronisation."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    _chk_pnpl_lo_state(sc, st)
+    A, dev = _chk_active(sc, st.active, n_active), sc.device
+    if out is None:
+        out = (torch.empty((A, 27), dtype=torch.float64, device=dev), torch.empty((A, 45), dtype=torch.float64, device=dev),
+               torch.empty((A,), dtype=torch.int32, device=dev))
+    Bt, Qt, cnt = out
+    _chk(Bt, "out B27", torch.float64, (A, 27), dev)
+    _chk(Qt, "out Q45", torch.float64, (A, 45), dev)
+    _chk(cnt, "out cnt", torch.int32, (A,), dev)
+    _call("ransac_pnpl_lo", sc, "cvxpnpl_ransac_pnpl_lo_assemble", sc.F, A, _ptr(st.active), *_scene_args(sc), *_data_args(sc), _ptr(st.R), _ptr(st.t),
+          _ptr(sc.K), sc.per_scene_K, float(thresh_k), _ptr(Bt), _ptr(Qt), _ptr(cnt))
+    return Bt, Qt, cnt
+
+
+def lo_update_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, cap: int, confidence: float, fit, cnt, thresh: float = 2.0):
+    """cvxpnpl_ransac_pnpl_lo_update on the first n_active entries of st.active: lo_update_active with two masks.  The refit fit.R[a],
+    fit.t[a], fit.status[a] of the cnt[a] correspondences lo_assemble_pnpl_active took is counted at thresh over the scene's points and
+    lines and TAKEN when its status is 0 or 2, cnt[a] >= 4 and its count is at least max(st.best[f], st.head[f,1]) -- the non-minimal fit
+    wins a tie.  Then pose, head[f,0:2], best[f], the scene's slice of st.mask (points) and its slice of st.mask_lines change together,
+    head[f,2] stays and st.lo_taken[f] goes up by one.  Taken or not, st.done[a] |= the stopping rule at st.hyp_used[f], st.best[f] over
+    P_f + L_f.  In place, no synchronisation."""
+    _require_gpu()
+    _chk_pnpl_scenes(sc)
+    _chk_pnpl_lo_state(sc, st)
+    if getattr(st, "lo_taken", None) is None:
+        raise ValueError("state.lo_taken is missing: the state of a call with local optimisation goes through lo_init")
+    dev = sc.device
+    _chk(st.lo_taken, "state.lo_taken", torch.int32, (sc.F,), dev)
+    conf, _ = _check_adaptive(confidence, 1)
+    A = _chk_active(sc, st.active, n_active)
+    cp = int(cap)
+    if not 0 <= cp <= 0x7FFFFFFF:
+        raise ValueError(f"cap must be an int >= 0 (and below 2^31), got {cap!r}")
+    _chk(fit.R, "fit.R", torch.float64, (A, 3, 3), dev)
+    _chk(fit.t, "fit.t", torch.float64, (A, 3), dev)
+    _chk(fit.status, "fit.status", torch.int32, (A,), dev)
+    _chk(cnt, "cnt", torch.int32, (A,), dev)
+    _call("ransac_pnpl_lo", sc, "cvxpnpl_ransac_pnpl_lo_update", sc.F, A, _ptr(st.active), cp, conf, *_scene_args(sc), _ptr(fit.R), _ptr(fit.t),
+          _ptr(fit.status), _ptr(cnt), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
+          _ptr(st.best), _ptr(st.mask), _ptr(st.mask_lines), _ptr(st.hyp_used), _ptr(st.lo_taken), _ptr(st.done))
+
+
+def lo_assemble_pnpl_host(pts_2d, pts_3d, line_2d, line_3d, sizes, line_sizes, K, R, t, active, thresh_k: float, n_threads: int = 0):
+    """cvxpnpl_ransac_pnpl_lo_assemble_host: what lo_assemble_pnpl_active computes, on host arrays by the rules the kernel follows (the
+    same lanes, the same order of the sums).  pts_2d [sum P,2], pts_3d [sum P,3] packed with sizes, line_2d [sum L,2,2], line_3d
+    [sum L,2,3] packed with line_sizes (F ints each; a half may be None or empty), K [3,3] or [F,3,3], R [F,3,3], t [F,3] the running
+    poses, active: A scene indices.  Returns numpy (B27 [A,27], Q45 [A,45], cnt [A] int32); the rows of an entry outside [0, F) keep
+    their initial NaN / -1.  No GPU needed."""
+    import ctypes as C
+
+    ps, ls = [int(m) for m in sizes], [int(m) for m in line_sizes]
+    F, nP, nL = len(ps), sum(ps), sum(ls)
+    if F < 1 or len(ls) != F or any(m < 0 for m in ps + ls):
+        raise ValueError("sizes and line_sizes: at least one scene, as many of one as of the other, no negative size")
+    x = _np.ascontiguousarray(_np.zeros((0, 2)) if pts_2d is None else pts_2d, dtype=_np.float64).reshape(-1, 2)
+    X = _np.ascontiguousarray(_np.zeros((0, 3)) if pts_3d is None else pts_3d, dtype=_np.float64).reshape(-1, 3)
+    l2 = _np.ascontiguousarray(_np.zeros((0, 2, 2)) if line_2d is None else line_2d, dtype=_np.float64).reshape(-1, 2, 2)
+    l3 = _np.ascontiguousarray(_np.zeros((0, 2, 3)) if line_3d is None else line_3d, dtype=_np.float64).reshape(-1, 2, 3)
+    Kh = _np.ascontiguousarray(K, dtype=_np.float64)
+    Rh = _np.ascontiguousarray(R, dtype=_np.float64)
+    th = _np.ascontiguousarray(t, dtype=_np.float64)
+    act = _np.ascontiguousarray(active, dtype=_np.int32)
+    if x.shape[0] != nP or X.shape[0] != nP:
+        raise ValueError(f"packed points: expected [{nP},2] and [{nP},3], got {x.shape} and {X.shape}")
+    if l2.shape[0] != nL or l3.shape[0] != nL:
+        raise ValueError(f"packed lines: expected [{nL},2,2] and [{nL},2,3], got {l2.shape} and {l3.shape}")
+    if Kh.shape != (3, 3) and Kh.shape != (F, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{F},3,3], got {Kh.shape}")
+    if Rh.shape != (F, 3, 3) or th.shape != (F, 3):
+        raise ValueError(f"R must be [{F},3,3] and t [{F},3], got {Rh.shape} and {th.shape}")
+    if act.ndim != 1:
+        raise ValueError(f"active must have one dimension, got shape {act.shape}")
+    A = act.shape[0]
+    off_p, off_l = _np.zeros(F + 1, dtype=_np.int64), _np.zeros(F + 1, dtype=_np.int64)
+    _np.cumsum(ps, out=off_p[1:])
+    _np.cumsum(ls, out=off_l[1:])
+    Bt, Qt, cnt = _np.full((A, 27), _np.nan), _np.full((A, 45), _np.nan), _np.full(A, -1, dtype=_np.int32)
+    L = _lib.ransac_pnpl_lo_lib()
+    ptr = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)  # noqa: E731
+    rc = L.cvxpnpl_ransac_pnpl_lo_assemble_host(F, A, ptr(act), ptr(off_p), nP, ptr(off_l), nL, ptr(x), ptr(X), ptr(l2), ptr(l3), ptr(Rh), ptr(th), ptr(Kh),
+                                                int(Kh.ndim == 3), float(thresh_k), ptr(Bt), ptr(Qt), ptr(cnt), int(n_threads))
+    if rc != 0:
+        raise RuntimeError(f"cvxpnpl_ransac_pnpl_lo_assemble_host failed ({rc}): {L.cvxpnpl_ransac_pnpl_lo_last_error().decode()}")
+    return Bt, Qt, cnt
+
 
 def _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, packed_p, packed_l, n_hyp):
     """Host-side validation of the guided keywords of ransac_pnpl_batch (nothing here needs a GPU): returns pool_full (None for an
@@ -1221,7 +1327,7 @@ def _pack_quality(q, packed, device):
 def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, thresh: float = 2.0, max_iters: int = 100, eps: float = 1e-6, seed=0,
                       refit: bool = True, refit_rounds: int = 1, sizes=None, line_sizes=None, device=None, polish: bool = False,
                       confidence: Optional[float] = None, round_hyp: int = 64, quality=None, line_quality=None, pool_full: Optional[int] = None,
-                      **solver_opts):
+                      local_opt: int = 0, lo_widen: float = 1.0, **solver_opts):
     """Robust PnPL for F scenes of different sizes in one launch sequence; the argument order is pnpl's.
 
     Scenes: lists of F arrays pts_2d[f] [P_f,2] / pts_3d[f] [P_f,3] / line_2d[f] [L_f,2,2] / line_3d[f] [L_f,2,3], or packed arrays with
@@ -1246,11 +1352,24 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
     ranked once (rank_pnpl_scenes) and hypothesis h draws its minimal set from the pool_size(h, P_f + L_f, pool_full) best-ranked
     correspondences while h < pool_full; from there on the draws are the uniform ones.  pool_full (an int >= 0) defaults to n_hyp; 0 is
     the uniform sampler bit for bit.  With confidence the stopping rule is unchanged and counts inliers of the whole scene.  The result
-    gains pool_full."""
+    gains pool_full.
+    local_opt (an int >= 0; 0: the code above unchanged, and today's result key for key; needs confidence): LO-RANSAC as in
+    ransac_pnp_batch, on the UNION of a scene's points and lines.  Every round ends with local_opt steps over the scenes still active:
+    the points and lines within thresh * m_k of a scene's running pose are assembled into a cost (lo_assemble_pnpl_active), the costs
+    are solved by solve_cost_batch with this call's eps / max_iters / solver options, and a refit of status 0 or 2, fitted to at least
+    four correspondences, that counts -- at thresh, points plus lines -- at least the running best replaces it, a tie going to the fit
+    (lo_update_pnpl_active); the stopping rule then reads that count.  The refits do NOT go through solve_minimal_costs:
+    MINIMAL_SOLVER_OPTS exists for the costs of four correspondences, and a consensus set is over-determined -- the case the solver's
+    launch plan assumes at the cost seam.  m_k falls from lo_widen (a float >= 1) in the first step to 1 in the last (lo_thresholds).
+    The draws do not depend on it, and a later round's minimal hypothesis replaces the running best only by a strictly higher count, so
+    no scene draws more than without it.  quality / line_quality compose unchanged: they only change the draws.  The result gains
+    lo_taken [F] (host int32: refits taken per scene), local_opt and lo_widen; best_index stays the index of the minimal hypothesis
+    that seeded the running pose."""
     ps, ls = _check_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes, line_sizes)
     F = len(ps)
     seeds, conf, round_hyp = _batch_head(F, seed, n_hyp, confidence, round_hyp)
     pool_full = _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, sizes is not None, line_sizes is not None, n_hyp)
+    local_opt, lo_widen = _check_local_opt(local_opt, lo_widen, confidence, "count")  # (after every earlier check: the order of their errors is pinned)
     sc = pack_pnpl_scenes(pts_2d, line_2d, pts_3d, line_3d, K, sizes=sizes, line_sizes=line_sizes, device=device, seeds=seeds)
     order = None
     if pool_full is not None:  # the ranking of every scene's union: once per call, before the launch sequence
@@ -1263,8 +1382,19 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
     if conf is not None:
         cap = int(n_hyp)
         stage = lambda act, A, h0, Hr: solve(*sample_assemble_active(sc, act, A, h0, Hr, cap, order, pool_full or 0))  # noqa: E731
-        state = adaptive_pnpl_init(sc)
-        adaptive = (state, _rounds(sc, state, (stage, score_pnpl_active, update_pnpl_active), cap, conf, round_hyp, thresh), conf)
+        lo_steps = None
+        if local_opt:  # the rounds as without it, each ending in local_opt refits of the running bests
+            state = lo_init(sc, adaptive_pnpl_init(sc))
+            steps = lo_thresholds(thresh, local_opt, lo_widen)
+
+            def lo_steps(A):
+                for thresh_k in steps:
+                    Bt, Qt, cnt = lo_assemble_pnpl_active(sc, state, A, thresh_k)
+                    fit = solve_cost_batch(Qt, Bt, eps=eps, max_iters=max_iters, device=sc.device, **solver_opts)
+                    lo_update_pnpl_active(sc, state, A, cap, conf, fit, cnt, thresh)
+        else:
+            state = adaptive_pnpl_init(sc)
+        adaptive = (state, _rounds(sc, state, (stage, score_pnpl_active, update_pnpl_active), cap, conf, round_hyp, thresh, after_update=lo_steps), conf)
         R, t, head, mp, ml = state.R, state.t, state.head, state.mask, state.mask_lines
     else:  # no torch kernel from here to the read-back: draw + minimal assembly, the F * n_hyp minimal solves at the cost seam ...
         if order is None:
@@ -1273,8 +1403,11 @@ def ransac_pnpl_batch(pts_2d, line_2d, pts_3d, line_3d, K, n_hyp: int = 1024, th
             res = solve(*sample_assemble_active(sc, torch.arange(F, dtype=torch.int32, device=sc.device), F, 0, int(n_hyp), int(n_hyp), order, pool_full))
         count = score_pnpl_scenes(sc, res.R, res.t, thresh, status=res.status, usable=(0, 2))
         R, t, head, mp, ml = select_pnpl_scenes(sc, count, res.R, res.t, res.status, thresh)
-    return _finish(sc, (assemble_pnpl_consensus, refit_update_pnpl_scenes, (("inliers_pts", "offsets"), ("inliers_lines", "line_offsets"))), R, t, head,
-                   (mp, ml), thresh, refit, refit_rounds, polish, n_hyp, adaptive, pool_full)
+    out = _finish(sc, (assemble_pnpl_consensus, refit_update_pnpl_scenes, (("inliers_pts", "offsets"), ("inliers_lines", "line_offsets"))), R, t, head,
+                  (mp, ml), thresh, refit, refit_rounds, polish, n_hyp, adaptive, pool_full)
+    if local_opt:  # (the call without local optimisation keeps exactly its keys)
+        out.update(lo_taken=state.lo_taken.cpu(), local_opt=local_opt, lo_widen=lo_widen)
+    return out
 
 
 def ransac_pnl_batch(line_2d, line_3d, K, **kw):
@@ -1286,7 +1419,7 @@ def ransac_pnpl(pts_2d, line_2d, pts_3d, line_3d, K, **kw):
     """Robust PnPL for ONE scene: pts_2d [P,2], line_2d [L,2,2], pts_3d [P,3], line_3d [L,2,3] (either pair may be None), K [3,3].  The
     batch call with F = 1 (scene 0 uses `seed` itself), unpacked: R [3,3], t [3], inliers_pts [P], inliers_lines [L] on the device;
     n_inliers, status, n_certified, best_index (ints), n_hyp.  The adaptive and guided keywords pass through (quality [P], line_quality
-    [L]); hyp_used is then an int."""
+    [L]); hyp_used is then an int, and so is lo_taken of a call with local_opt."""
     for k in ("quality", "line_quality"):
         if kw.get(k) is not None:
             kw[k] = [kw[k]]
@@ -1299,6 +1432,8 @@ def ransac_pnpl(pts_2d, line_2d, pts_3d, line_3d, K, **kw):
         one.update(hyp_used=int(out["hyp_used"][0]), rounds=out["rounds"], confidence=out["confidence"])
     if "pool_full" in out:
         one["pool_full"] = out["pool_full"]
+    if "lo_taken" in out:
+        one.update(lo_taken=int(out["lo_taken"][0]), local_opt=out["local_opt"], lo_widen=out["lo_widen"])
     return one
 
 
