@@ -410,6 +410,12 @@ __device__ __forceinline__ double dot10_f64(const double (&a)[10], const double 
     for (int i = 2; i < 10; i += 2) { s0 = fma(a[i], b[i], s0); s1 = fma(a[i + 1], b[i + 1], s1); }
     return s0 + s1;
 }
+// cvxw::dot10 on operands that are already in registers: the same expression, so the same products, sums and contractions
+__device__ __forceinline__ double dot10_regs(const double2 (&a)[5], const double2 (&b)[5])
+{
+    return ((a[0].x * b[0].x + a[0].y * b[0].y) + (a[1].x * b[1].x + a[1].y * b[1].y)) + ((a[2].x * b[2].x + a[2].y * b[2].y) + (a[3].x * b[3].x + a[3].y * b[3].y)) +
+           (a[4].x * b[4].x + a[4].y * b[4].y);
+}
 __device__ __forceinline__ void jstep_dpp(double (&qd)[10], double &alq, bool real, bool tie_neg, bool active, double tol2, bool &coarse)
 {
     double oq[10];
@@ -459,8 +465,14 @@ __device__ __forceinline__ void jacobi_sweep(COL &q, T &al, unsigned atab, int g
 }
 
 // In-place LDL^T of the symmetric matrix held 3-4 entries per lane, pivot rows broadcast through LDS;
-// returns the smallest pivot (cvx::ldl_min_pivot).
-template <class OWN>
+// returns the smallest pivot (cvx::ldl_min_pivot).  It does not stop at a non-positive pivot: a zero or NaN one runs through the remaining rows.
+// AHEAD (the float64-sweep instantiations, as in quad_proj): the pivot and the 2 EPL row entries of a step are read together behind the step's
+// fence, and an entry is updated by a select.  Written with the branch, the compiler sank each entry's two reads into the EXEC-masked arm of
+// its "ei > k" and waited for each alone: 1 + 2 EPL LDS round trips in a row per pivot, ten pivots per attempt
+// (profiles/r09/quad_attempt_lds_ab.txt).  The empty asm keeps the reads out of the arms.  Per entry (ra id) rb and then the subtraction as one
+// fma -- what the compiler made of "Me -= ra * id * rb"; written out so that it stays that.  (A lane reads C_ROW entries of rows <= k that
+// this step did not write -- stale, possibly NaN -- exactly where its update is not selected.)
+template <bool AHEAD = false, class OWN>
 __device__ __forceinline__ double quad_ldl(double *L, const OWN &w, double *Me)
 {
     double minp = 1e300;
@@ -471,12 +483,27 @@ __device__ __forceinline__ double quad_ldl(double *L, const OWN &w, double *Me)
             if (w.ok(m) && w.ei(m) == k) L[C_ROW + w.ej(m)] = Me[m];
         CVXW_SYNC();
         const double d = L[C_ROW + k];
-        minp = d < minp ? d : minp;
-        const double id = cvxw::fast_rcp(d);
+        if constexpr (AHEAD) {
+            double ra[OWN::EPL], rb[OWN::EPL];
 #pragma unroll
-        for (int m = 0; m < OWN::EPL; ++m) {
-            const double ra = L[C_ROW + w.ei(m)], rb = L[C_ROW + w.ej(m)];
-            if (w.ei(m) > k) Me[m] -= ra * id * rb;
+            for (int m = 0; m < OWN::EPL; ++m) { ra[m] = L[C_ROW + w.ei(m)]; rb[m] = L[C_ROW + w.ej(m)]; }
+#pragma unroll
+            for (int m = 0; m < OWN::EPL; ++m) asm volatile("" : "+v"(ra[m]), "+v"(rb[m]));
+            minp = d < minp ? d : minp;
+            const double id = cvxw::fast_rcp(d);
+#pragma unroll
+            for (int m = 0; m < OWN::EPL; ++m) {
+                const double u = fma(-(ra[m] * id), rb[m], Me[m]);
+                Me[m] = (w.ei(m) > k) ? u : Me[m];
+            }
+        } else {
+            minp = d < minp ? d : minp;
+            const double id = cvxw::fast_rcp(d);
+#pragma unroll
+            for (int m = 0; m < OWN::EPL; ++m) {
+                const double ra = L[C_ROW + w.ei(m)], rb = L[C_ROW + w.ej(m)];
+                if (w.ei(m) > k) Me[m] -= ra * id * rb;
+            }
         }
         CVXW_SYNC();
     }
@@ -1102,12 +1129,55 @@ CVXQ_PH(3); /* check: top eigenvector, reuse test */
                         for (int i = 0; i < 9; ++i) L[C_RL + i] = Rc[i];
                     }
                     CVXW_SYNC();
+                    // F64SW: every read of these two stages is issued before the stage's first write (an LDS write cannot be passed by a later read of
+                    // the same array, and each write waits for the arithmetic in front of it: written entry by entry, the reads of entry m + 1 left
+                    // only after the dot product of entry m -- M36 round trips in a row per Newton iteration, M40 for the x-vectors;
+                    // profiles/r09/quad_attempt_lds_ab.txt).  The empty asm keeps the x-vector reads out of their entries' EXEC-masked arms.  The values
+                    // and the order of the operations on them are the entry-by-entry code's (cvxw::dot10's).
+                    if constexpr (F64SW) {
+                        double rl[G_::M40];
+#pragma unroll
+                        for (int m = 0; m < G_::M40; ++m) rl[m] = L[C_RL + xsrc[m]];
+#pragma unroll
+                        for (int m = 0; m < G_::M40; ++m) asm volatile("" : "+v"(rl[m]));
+#pragma unroll
+                        for (int m = 0; m < G_::M40; ++m) {
+                            const int idx = gl + LPP * m;
+                            if (idx < 40) L[C_XV + idx] = (idx == 9) ? 1.0 : xsgn[m] * rl[m];
+                        }
+                    } else {
 #pragma unroll
                     for (int m = 0; m < G_::M40; ++m) {
                         const int idx = gl + LPP * m;
                         if (idx < 40) L[C_XV + idx] = (idx == 9) ? 1.0 : xsgn[m] * L[C_RL + xsrc[m]];
                     }
+                    }
                     CVXW_SYNC();
+                    if constexpr (F64SW && MODE == 0) {
+                        // Two register sets (as in W+): entries 0 and 1 are read together; entry m + 2 is read into the set of entry m once its dot
+                        // product is taken and BEFORE that product is written.  (All M36 entries at once is 120 registers and spilled: scratch 124 ->
+                        // 140 B per lane.  MODE 2 keeps the entry-by-entry code: the second set takes <2,2,16,true,0> from 211 to 234 registers, past
+                        // what tests/golden/kernel_resources.json allows.)
+                        double2 qa[2][5], xb[2][5];
+                        auto rd = [&](int m, double2 (&a_)[5], double2 (&b_)[5]) {
+                            const int idx = gl + LPP * m < 36 ? gl + LPP * m : 0; // (a lane without an entry m reads entry 0's operands and writes nothing)
+                            const int vv = idx / 9, i = idx % 9;
+#pragma unroll
+                            for (int j = 0; j < 5; ++j) { a_[j] = L2[(Q_QF + i * 10) / 2 + j]; b_[j] = L2[(C_XV + vv * 10) / 2 + j]; }
+                        };
+                        rd(0, qa[0], xb[0]);
+                        if (G_::M36 > 1) rd(1, qa[1], xb[1]);
+#pragma unroll
+                        for (int m = 0; m < G_::M36; ++m) {
+                            const double yv = dot10_regs(qa[m & 1], xb[m & 1]);
+                            if (m + 2 < G_::M36) {
+                                __builtin_amdgcn_sched_barrier(0);
+                                rd(m + 2, qa[m & 1], xb[m & 1]);
+                            }
+                            const int idx = gl + LPP * m;
+                            if (idx < 36) L[C_YV + (idx / 9) * 10 + idx % 9] = yv;
+                        }
+                    } else {
 #pragma unroll
                     for (int m = 0; m < G_::M36; ++m) {
                         const int idx = gl + LPP * m;
@@ -1115,6 +1185,7 @@ CVXQ_PH(3); /* check: top eigenvector, reuse test */
                             const int vv = idx / 9, i = idx % 9;
                             L[C_YV + vv * 10 + i] = cvxw::dot10(L2 + (Q_QF + i * 10) / 2, L2 + (C_XV + vv * 10) / 2);
                         }
+                    }
                     }
                     if (gl < 4) L[C_YV + gl * 10 + 9] = 0.0;
                     CVXW_SYNC();
@@ -1210,8 +1281,20 @@ CVXQ_PH(4); /* polar + Newton polish */
             double S[EPL];
             {
                 double T[EPL];
+                if constexpr (F64SW) {
+                    // the EPL cost entries read together and selected (row 9 / column 9 of Q_QF are read and dropped): each was read and waited on alone
+                    // in the EXEC-masked arm of its "ej < 9"
+                    double qf[EPL];
+#pragma unroll
+                    for (int m = 0; m < EPL; ++m) qf[m] = L[Q_QF + w.ei(m) * 10 + w.ej(m)];
+#pragma unroll
+                    for (int m = 0; m < EPL; ++m) asm volatile("" : "+v"(qf[m]));
+#pragma unroll
+                    for (int m = 0; m < EPL; ++m) { S[m] = rho * (Wp[m] - W[m]); T[m] = S[m] - (w.ej(m) < 9 ? qf[m] : 0.0); }
+                } else {
 #pragma unroll
                 for (int m = 0; m < EPL; ++m) { S[m] = rho * (Wp[m] - W[m]); T[m] = S[m] - (w.ej(m) < 9 ? L[Q_QF + w.ei(m) * 10 + w.ej(m)] : 0.0); }
+                }
                 quad_proj<VAR, F64SW>(L, w, T, 0.0);
 #pragma unroll
                 for (int m = 0; m < EPL; ++m) {
@@ -1235,10 +1318,24 @@ CVXQ_PH(4); /* polar + Newton polish */
             CVXW_SYNC();
             {   // S2 = S1 - P_range(sym(lam z^T))
                 double E[EPL], Nn[EPL];
+                if constexpr (F64SW) {
+                    // the 4 EPL operands read together (each entry's four were read and waited on in the EXEC-masked arm of its "odd" select)
+                    double li[EPL], xj[EPL], xi[EPL], lj[EPL];
+#pragma unroll
+                    for (int m = 0; m < EPL; ++m) { li[m] = L[C_LAM + w.ei(m)]; xj[m] = L[C_XV + w.ej(m)]; xi[m] = L[C_XV + w.ei(m)]; lj[m] = L[C_LAM + w.ej(m)]; }
+#pragma unroll
+                    for (int m = 0; m < EPL; ++m) asm volatile("" : "+v"(li[m]), "+v"(xj[m]), "+v"(xi[m]), "+v"(lj[m]));
+#pragma unroll
+                    for (int m = 0; m < EPL; ++m) {
+                        E[m] = odd[m] ? 0.0 : 0.5 * (li[m] * xj[m] + xi[m] * lj[m]);
+                        Nn[m] = E[m];
+                    }
+                } else {
 #pragma unroll
                 for (int m = 0; m < EPL; ++m) {
                     E[m] = odd[m] ? 0.0 : 0.5 * (L[C_LAM + w.ei(m)] * L[C_XV + w.ej(m)] + L[C_XV + w.ei(m)] * L[C_LAM + w.ej(m)]);
                     Nn[m] = E[m];
+                }
                 }
                 quad_proj<VAR, F64SW>(L, w, Nn, 0.0);
 #pragma unroll
@@ -1251,16 +1348,24 @@ CVXQ_PH(4); /* polar + Newton polish */
             double res, zSz;
             {
                 const int aa = gl < 10 ? gl : 0;
+                if constexpr (F64SW) {
+                    double za = L[C_XV + aa]; // (read with the dot product's operands, not alone in the arm of "gl < 10" behind it)
+                    const double sz = cvxw::dot10(L2 + (Q_WF + aa * 10) / 2, L2 + C_XV / 2);
+                    asm volatile("" : "+v"(za));
+                    res = grp_max<LPP>(L, gl, gl < 10 ? fabs(sz) : 0.0);
+                    zSz = grp_sum<LPP>(L, gl, gl < 10 ? za * sz : 0.0);
+                } else {
                 const double sz = cvxw::dot10(L2 + (Q_WF + aa * 10) / 2, L2 + C_XV / 2);
                 res = grp_max<LPP>(L, gl, gl < 10 ? fabs(sz) : 0.0);
                 zSz = grp_sum<LPP>(L, gl, gl < 10 ? L[C_XV + aa] * sz : 0.0);
+                }
             }
             CVXW_SYNC();
             double Se[EPL];
 #pragma unroll
             for (int m = 0; m < EPL; ++m) Se[m] = S[m] + (((w.pk[m] >> 23) & 1) ? delta : 0.0);
 CVXQ_PH(5); /* dual fit + correction */
-            const double minp = quad_ldl(L, w, Se);
+            const double minp = quad_ldl<F64SW>(L, w, Se);
             const bool pre = (res < 1e-10) && (d0 > 0) && (pobj == pobj);
             // (The eigen-gradient step of the dual, cvx::dual_refine_step, is NOT made here -- measured, round 6, profiles/r06/refine_ab3.txt: with the
             //  step in this phase the four problems of a wavefront pay for it in lockstep whenever one of them fails, and the wavefronts that end
