@@ -17,7 +17,7 @@ DEPS = [SRC, HOST_SRC, LANE_SRC, *SOLVER_ENTRY_HEADERS, os.path.join(HERE, "csrc
         os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd.h")]
 
 
-RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the seven RANSAC entry files share
+RANSAC_ENTRY_DEPS = [os.path.join(HERE, "csrc", "ransac_entry.h"), ENTRY_ERROR_H]  # what the nine RANSAC entry files share
 
 
 def hipcc():
@@ -59,7 +59,7 @@ def grad_compile_cmd(out=GRAD_OUT):
 RANSAC_SRC = os.path.join(HERE, "csrc", "ransac_hip.hip")
 RANSAC_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac.so")
 RANSAC_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac.resources.txt")
-RANSAC_DEPS = [RANSAC_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
+RANSAC_DEPS = [RANSAC_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_kernel.h"), os.path.join(HERE, "csrc", "ransac_assemble_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac.h")]
 
 
@@ -73,7 +73,7 @@ RANSAC_PNPL_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_hip.hip")
 RANSAC_PNPL_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.so")
 RANSAC_PNPL_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl.resources.txt")
 RANSAC_PNPL_DEPS = [RANSAC_PNPL_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_pnpl_kernel.h"), os.path.join(HERE, "csrc", "ransac_pnpl_common.h"),
-                    os.path.join(HERE, "csrc", "ransac_common.h"),
+                    os.path.join(HERE, "csrc", "ransac_assemble_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                     os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                     os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_pnpl.h")]
 
@@ -233,7 +233,7 @@ RANSAC_LO_SRC = os.path.join(HERE, "csrc", "ransac_lo_hip.hip")
 RANSAC_LO_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_lo.so")
 RANSAC_LO_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_lo.resources.txt")
 RANSAC_LO_SOURCES = [RANSAC_LO_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_lo_kernel.h"), os.path.join(HERE, "csrc", "ransac_lo_core.h"),
-                     os.path.join(HERE, "csrc", "ransac_adaptive_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
+                     os.path.join(HERE, "csrc", "ransac_assemble_core.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"), os.path.join(HERE, "csrc", "ransac_common.h"),
                      os.path.join(HERE, "csrc", "solver_core.h"), os.path.join(HERE, "csrc", "problem_io.h"),
                      os.path.join(HERE, "csrc", "host_pool.h"), os.path.join(os.path.dirname(HERE), "include", "cvxpnpl_amd_ransac_lo.h")]
 
@@ -249,7 +249,7 @@ RANSAC_PNPL_LO_SRC = os.path.join(HERE, "csrc", "ransac_pnpl_lo_hip.hip")
 RANSAC_PNPL_LO_OUT = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_lo.so")
 RANSAC_PNPL_LO_RESOURCES = os.path.join(HERE, "libcvxpnpl_amd_ransac_pnpl_lo.resources.txt")
 RANSAC_PNPL_LO_SOURCES = [RANSAC_PNPL_LO_SRC, *RANSAC_ENTRY_DEPS, os.path.join(HERE, "csrc", "ransac_pnpl_lo_kernel.h"),
-                          os.path.join(HERE, "csrc", "ransac_pnpl_lo_core.h"), os.path.join(HERE, "csrc", "ransac_lo_core.h"),
+                          os.path.join(HERE, "csrc", "ransac_pnpl_lo_core.h"), os.path.join(HERE, "csrc", "ransac_lo_core.h"), os.path.join(HERE, "csrc", "ransac_assemble_core.h"),
                           os.path.join(HERE, "csrc", "ransac_pnpl_common.h"), os.path.join(HERE, "csrc", "ransac_adaptive_core.h"),
                           os.path.join(HERE, "csrc", "ransac_common.h"), os.path.join(HERE, "csrc", "solver_core.h"),
                           os.path.join(HERE, "csrc", "problem_io.h"), os.path.join(HERE, "csrc", "host_pool.h"),

@@ -9,8 +9,8 @@
 // its argument block, never the block: one reference to the block changes a kernel's whole code.  score_points and block_argmax take
 // the type of their loop index from the caller, so that each kernel keeps the index width it had.  No kernel here: a library that
 // includes this header compiles nothing it does not launch.  (Left as copies, because the extraction changed a kernel's registers: the
-// consensus assembly, the refit rule, the round bookkeeping, the point half of cvxnl::block_inliers; and the arg-max of
-// cvxn::select_scenes_kernel -- DESIGN.md section 13.)
+// refit rule, the round bookkeeping, the point half of cvxnl::block_inliers; and the arg-max of cvxn::select_scenes_kernel -- DESIGN.md
+// section 13.  The assembly of a scene subset is ransac_assemble_core.h.)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>

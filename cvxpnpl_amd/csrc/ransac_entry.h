@@ -1,6 +1,7 @@
-// ransac_entry.h -- what the entry points of the seven RANSAC libraries (ransac, ransac_pnpl, ransac_adaptive, ransac_guided,
-// ransac_pnpl_adaptive, ransac_msac, ransac_lo) share around their kernels: the error text, the argument contract of a scenes call and of a round, and the launch
-// of a kernel whose grid is (hypotheses, scenes or active entries).  Host-only.  Every function is inline and hidden: each library keeps
+// ransac_entry.h -- what the entry points of the nine RANSAC libraries (ransac, ransac_pnpl, ransac_adaptive, ransac_guided,
+// ransac_pnpl_adaptive, ransac_msac, ransac_lo, ransac_pnpl_lo) share around their kernels: the error text, the argument contract of a
+// scenes call and of a round, the pointers of a call by name, and the launch of a kernel whose grid is (hypotheses, scenes or active
+// entries).  Host-only.  Every function is inline and hidden: each library keeps
 // a copy of its own -- its own thread-local message -- and exports nothing of this.
 //
 // The checks return a message or null; an entry point runs them in this order: the sizes and -- a call that launches -- the pointers of
@@ -101,6 +102,16 @@ CVXNE_FN const char *check_pnpl_round(int64_t n_scenes, int64_t n_active, const 
     }
     fill_scene_set(s, n_scenes, off_p, n_pts, off_l, n_lines, p2, p3, l2, l3);
     return nullptr;
+}
+
+// the pointers of a call that launches, each under its own name: the first null one becomes the message
+struct Named { const char *name; const void *p; };
+template <int N>
+CVXNE_FN int null_among(const char *who, const Named (&ptrs)[N])
+{
+    for (const Named &n : ptrs)
+        if (!n.p) return cvxee::fail(-1, "%s: bad arguments (%s is null)", who, n.name);
+    return 0;
 }
 
 // the budget of a round: hypotheses hyp0 .. hyp0 + n_round - 1 of at most cap

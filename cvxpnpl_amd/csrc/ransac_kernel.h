@@ -10,13 +10,14 @@
 #include <stdint.h>
 
 #include "problem_io.h"
+#include "ransac_assemble_core.h"
 #include "ransac_common.h"
 #include "solver_core.h"
 
 namespace cvxn {
 
 // (SCENE_BLOCK, the lanes of every workgroup here, SCENE_WAVES, POINT_TILE and the steps the kernels call: ransac_common.h; those of the
-// consensus assembly: ransac_consensus.h)
+// consensus assembly: ransac_assemble_core.h)
 
 // ---- sampling: one lane per (scene, hypothesis), grid (ceil(H / 256), scenes).  The draw of cvxs::sample_sets_kernel for k = 4 over the
 // scene's own M_f, with the scene's own seed as the Philox key and the hypothesis index WITHIN the scene as the counter: scene f draws
@@ -136,7 +137,8 @@ __global__ void __launch_bounds__(SCENE_BLOCK) select_scenes_kernel(SelectScenes
 // serially: the wrong shape for a few hundred scenes of 10^3 correspondences.)  The lanes stride over the scene's correspondences, each
 // with Gram sums of its own; the sums meet in a fixed-order XOR butterfly, after which every lane holds the same total -- the result
 // does not depend on anything but the inputs.  The centre of the sums is the median of the subset's own first three selected records
-// (cvx::shift_centre; any centre is exact).  Fewer than three selected: NaN, as cvx::assemble reports a singular N^T N.
+// (cvxas::centre; any centre is exact).  Fewer than three selected: NaN, as cvx::assemble reports a singular N^T N.  The centre, the
+// butterfly, the finish and the store are ransac_assemble_core.h: the LO assemblies follow the same ones.
 struct ConsensusArgs {
     int64_t n_scenes, n_total;
     const int64_t *off;
@@ -147,7 +149,6 @@ struct ConsensusArgs {
     double *B27, *Q45;       // [n_scenes][27], [n_scenes][45]
     int32_t *count;          // [n_scenes]
 };
-__device__ inline double wave_xor_add(double v, int o) { return v + __shfl_xor(v, o); }
 __global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
 {
     const int64_t f = blockIdx.x;
@@ -160,31 +161,10 @@ __global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
 #pragma unroll
     for (int i = 0; i < 9; ++i) Kc[i] = a.K[(a.K_per_scene ? f * 9 : 0) + i];
     cvx::inv3(Kc, Ki, det);
-    // the first three selected correspondences, in scene order: ballots over chunks of 64 (wave-uniform)
-    int first[3] = {0, 0, 0}, nf = 0;
-    for (int base = 0; base < sl.n && nf < 3; base += 64) {
-        const int m = base + lane;
-        unsigned long long b = __ballot(m < sl.n && mk[m] != 0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (b != 0 && nf < 3) {
-                const int pos = base + __ffsll((long long)b) - 1;
-                first[0] = nf == 0 ? pos : first[0]; first[1] = nf == 1 ? pos : first[1]; first[2] = nf == 2 ? pos : first[2];
-                ++nf;
-                b &= b - 1;
-            }
-        }
-    }
-    double c[3] = {0.0, 0.0, 0.0};
-    if (nf > 0) {
-        double first3[9];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { // (entries beyond nf repeat the first record and are not read by shift_centre)
-            const int m = k < nf ? first[k] : first[0];
-            first3[3 * k] = s3[3 * m]; first3[3 * k + 1] = s3[3 * m + 1]; first3[3 * k + 2] = s3[3 * m + 2];
-        }
-        cvx::shift_centre(nf, first3, 0, nullptr, c);
-    }
+    int first[3] = {0, 0, 0}; // the first three selected correspondences, in scene order (wave-uniform)
+    const int nf = cvxas::wave_first(sl.n, 3, first, [&](int64_t m) { return mk[m] != 0; });
+    double c[3];
+    cvxas::centre(nf, first, s3, c);
     cvx::Gram g;
     cvx::gram_zero(g);
     int n = 0;
@@ -193,33 +173,10 @@ __global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
         cvx::gram_add_point(g, Ki, s2[2 * m], s2[2 * m + 1], s3[3 * m] - c[0], s3[3 * m + 1] - c[1], s3[3 * m + 2] - c[2]);
         ++n;
     }
-#pragma unroll 1
-    for (int o = 1; o < 64; o <<= 1) { // (rolled: six passes over the same 60 sums)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) g.M0[i] = wave_xor_add(g.M0[i], o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g.M1[k][i] = wave_xor_add(g.M1[k][i], o);
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g.M2[k][i] = wave_xor_add(g.M2[k][i], o);
-        n += __shfl_xor(n, o);
-    }
+    cvxas::wave_butterfly(g, n);
     double B[27], Q9[45];
-    const bool ok = n >= 3 && cvx::gram_finish(g, B, Q9) && (det == det) && det != 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) B[i * 9 + 3 * j + i] += c[j];
-    if (lane == 0) { // (every lane holds the same values; static indices keep B and Q9 in registers)
-#pragma unroll
-        for (int i = 0; i < 27; ++i) a.B27[f * 27 + i] = ok ? B[i] : NAN;
-#pragma unroll
-        for (int i = 0; i < 45; ++i) a.Q45[f * 45 + i] = ok ? Q9[i] : NAN;
-        a.count[f] = n;
-    }
+    const bool ok = cvxas::finish(g, n, det, c, B, Q9);
+    if (lane == 0) cvxas::store_cost(ok, B, Q9, n, f, a.B27, a.Q45, a.count); // (every lane holds the same values)
 }
 
 // ---- refit update: ONE workgroup per scene, the rule of cvxs::refit_update_kernel.  The refitted pose of the scene's consensus set is
@@ -255,8 +212,7 @@ __global__ void __launch_bounds__(SCENE_BLOCK) refit_update_scenes_kernel(RefitS
     __syncthreads();
     if (!take) return;
     (void)block_inliers(cam, sl.n, s2, s3, th2, a.mask + sl.beg, red); // pose and mask change together
-    if (threadIdx.x < 9) a.io_R[f * 9 + threadIdx.x] = a.fit_R[f * 9 + threadIdx.x];
-    if (threadIdx.x < 3) a.io_t[f * 3 + threadIdx.x] = a.fit_t[f * 3 + threadIdx.x];
+    take_pose(a.fit_R, a.fit_t, f, a.io_R, a.io_t, f);
     if (threadIdx.x == 0) { a.head[f * 4] = st; a.head[f * 4 + 1] = n_new; }
 }
 

@@ -1,14 +1,13 @@
 // ransac_lo_core.h -- the rules of local optimisation in adaptive RANSAC (include/cvxpnpl_amd_ransac_lo.h), ONE
 // statement of them for the device (lo_assemble_active_kernel, lo_update_active_kernel) and the host (cvxpnpl_ransac_lo_assemble_host):
-// which correspondences a step takes, the centre of their Gram sums, which lane adds which correspondence and in which order the partial
-// sums meet, and when a refitted pose is taken.
+// which correspondences a step takes, which lane adds which correspondence, and when a refitted pose is taken.  The centre of the Gram
+// sums, the order in which the partial sums meet, the finish and the NaN rule are ransac_assemble_core.h.
 //
 // The assembly of one active entry, by LANES = 256 lanes in four wavefronts:
 //   taken(m)  = the inlier predicate of cvxn::is_inlier at the scene's running pose, threshold th2 = (thresh * m_k)^2
-//   centre    = cvx::shift_centre of the first three taken correspondences in scene order (any centre is exact)
+//   centre    = cvxas::centre of the first three taken correspondences in scene order
 //   lane l    adds the taken correspondences m = l, l + 256, l + 512, ... in that order           (lane_sums)
-//   a wave    adds its 64 lanes' sums in the XOR butterfly o = 1, 2, 4, 8, 16, 32                 (v <- v + v[lane ^ o])
-//   the entry adds the four waves' sums in wave order, ((w0 + w1) + w2) + w3                      (waves_total)
+//   a wave, the entry: cvxas::wave_butterfly and cvxas::waves_total
 // so the 60 sums depend on the inputs alone.  On the device the camera and the predicate ARE cvxn::camera_load and cvxn::is_inlier; those
 // are device-only, so the host build restates them expression by expression (as ransac_msac_core.h does).
 #pragma once
@@ -18,15 +17,15 @@
 
 #include "problem_io.h"
 #include "ransac_adaptive_core.h"
+#include "ransac_assemble_core.h"
 #include "ransac_common.h"
 #include "solver_core.h"
 
 namespace cvxnlo {
 
-constexpr int LANES = cvxn::SCENE_BLOCK;  // lanes of an assembly: the family's workgroup
-constexpr int WAVES = cvxn::SCENE_WAVES;
-constexpr int GRAM = 60;                  // doubles of a cvx::Gram
-static_assert(sizeof(cvx::Gram) == GRAM * sizeof(double), "a Gram is 60 doubles and nothing else");
+using cvxas::GRAM;
+using cvxas::LANES;  // lanes of an assembly: the family's workgroup
+using cvxas::WAVES;
 
 // ---- the camera of a pose and the predicate
 __host__ __device__ inline void camera(const double *Rp, const double *tp, const double *Kp, cvxn::Camera &c)
@@ -59,20 +58,6 @@ __host__ __device__ inline bool taken(const cvxn::Camera &c, const double *s2, c
 #endif
 }
 
-// ---- the centre: cvx::shift_centre of the nf <= 3 first taken correspondences first[0 .. nf) (scene order); none taken: the origin
-__host__ __device__ inline void centre(int nf, const int *first, const double *s3, double *c)
-{
-    c[0] = c[1] = c[2] = 0.0;
-    if (nf <= 0) return;
-    double first3[9];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { // (entries beyond nf repeat the first record and are not read by shift_centre)
-        const int m = k < nf ? first[k] : first[0];
-        first3[3 * k] = s3[3 * m]; first3[3 * k + 1] = s3[3 * m + 1]; first3[3 * k + 2] = s3[3 * m + 2];
-    }
-    cvx::shift_centre(nf, first3, 0, nullptr, c);
-}
-
 // ---- lane l of an assembly: the Gram sums of the taken correspondences l, l + LANES, ... about the centre c; returns their number
 __host__ __device__ inline int lane_sums(int l, int n, const double *s2, const double *s3, const cvxn::Camera &cam, double th2, const double *Ki,
                                          const double *c, cvx::Gram &g)
@@ -87,33 +72,30 @@ __host__ __device__ inline int lane_sums(int l, int n, const double *s2, const d
     return cnt;
 }
 
-// ---- sum e of the entry from the WAVES wave sums part[w * stride + e], in wave order
-__host__ __device__ inline double waves_total(const double *part, int stride, int e)
-{
-    double tot = part[e];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) tot += part[w * stride + e];
-    return tot;
-}
-
-// ---- B27 and Q45 of the entry from its total sums: cvx::gram_finish, the centre put back into B; NaN for fewer than three taken, a
-// singular N^T N or a singular K -- what cvxn::assemble_consensus_kernel reports.  Returns whether the cost is usable.
-__host__ __device__ inline bool finish(const cvx::Gram &g, int n, double det, const double *c, double *B, double *Q9)
-{
-    const bool ok = n >= 3 && cvx::gram_finish(g, B, Q9) && (det == det) && det != 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) B[i * 9 + 3 * j + i] += c[j];
-    return ok;
-}
-
 // ---- the update: a refitted pose of status st, fitted to fit_cnt correspondences and counting n_new inliers at thresh, is TAKEN when it
 // is usable and holds at least the running best -- the rule of cvxn::refit_update_scenes_kernel: the non-minimal fit wins a tie.
 __host__ __device__ inline bool take_fit(int32_t st, int32_t fit_cnt, int32_t n_new, int32_t best, int32_t head_count)
 {
     const int32_t bar = best > head_count ? best : head_count;
     return (st == 0 || st == 2) && fit_cnt >= 4 && n_new >= bar;
+}
+
+// ---- the tail of an update, by every lane of the workgroup of entry ai (scene f of n_corr correspondences), which has counted n_new
+// inliers of the refit, decided `take` (workgroup-uniform) and, where taken, written the mask(s): pose, head[f][0..1], best[f] and
+// lo_taken[f] change together; taken or not, done[ai] |= scene_done at the scene's best: a flag that is set stays set.
+__device__ inline void commit_fit(bool take, int st, int n_new, int best_prev, int n_corr, const double *fit_R, const double *fit_t, int64_t ai,
+                                  double *io_R, double *io_t, int64_t f, int32_t *head, int32_t *best, int32_t *lo_taken, const int32_t *hyp_used,
+                                  int32_t cap, double confidence, int32_t *done)
+{
+    if (take) {
+        cvxn::take_pose(fit_R, fit_t, ai, io_R, io_t, f);
+        if (threadIdx.x == 0) {
+            head[f * 4] = st; head[f * 4 + 1] = n_new;
+            best[f] = n_new;
+            lo_taken[f] += 1;
+        }
+    }
+    if (threadIdx.x == 0 && cvxna::scene_done(hyp_used[f], cap, take ? n_new : best_prev, n_corr, confidence)) done[ai] = 1;
 }
 
 } // namespace cvxnlo

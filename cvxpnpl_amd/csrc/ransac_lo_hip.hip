@@ -1,10 +1,8 @@
 // ransac_lo_hip.hip -- entry points of local optimisation in adaptive RANSAC (include/cvxpnpl_amd_ransac_lo.h), built as
-// libcvxpnpl_amd_ransac_lo.so.  The kernels are ransac_lo_kernel.h, the rules ransac_lo_core.h, the shared checks ransac_entry.h.  Every
-// entry point checks its arguments before it launches anything.
+// libcvxpnpl_amd_ransac_lo.so.  The kernels are ransac_lo_kernel.h, the rules ransac_lo_core.h and ransac_assemble_core.h, the shared checks
+// ransac_entry.h.  Every entry point checks its arguments before it launches anything.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-
-#include <vector>
 
 #include "../../include/cvxpnpl_amd_ransac_lo.h"
 #include "host_pool.h"
@@ -15,19 +13,9 @@ using namespace cvxne;
 
 namespace {
 
-// the pointers of a call that launches, each under its own name: the first null one becomes the message
-struct Named { const char *name; const void *p; };
-template <int N>
-int null_among(const char *who, const Named (&ptrs)[N])
-{
-    for (const Named &n : ptrs)
-        if (!n.p) return cvxee::fail(-1, "%s: bad arguments (%s is null)", who, n.name);
-    return 0;
-}
-
-// one entry of the host assembly: the lanes, the butterflies and the wave order of lo_assemble_active_kernel, serially
-void assemble_entry(int64_t ai, int64_t f, const int64_t *off, int64_t n_total, const double *scene_2d, const double *scene_3d, const double *R,
-                    const double *t, const double *K, int32_t K_per_scene, double th2, double *B27, double *Q45, int32_t *count)
+// one entry of the host assembly: the first-three scan and the lanes of lo_assemble_active_kernel, the rest cvxas::assemble_entry
+void host_entry(int64_t ai, int64_t f, const int64_t *off, int64_t n_total, const double *scene_2d, const double *scene_3d, const double *R,
+                const double *t, const double *K, int32_t K_per_scene, double th2, double *B27, double *Q45, int32_t *count)
 {
     using namespace cvxnlo;
     const cvxn::Slice sl = cvxn::scene_slice(off, f, n_total);
@@ -41,27 +29,8 @@ void assemble_entry(int64_t ai, int64_t f, const int64_t *off, int64_t n_total, 
     for (int m = 0; m < sl.n && nf < 3; ++m)
         if (taken(cam, s2, s3, m, th2)) first[nf++] = m;
     double c[3];
-    centre(nf, first, s3, c);
-    std::vector<cvx::Gram> g(LANES);
-    std::vector<int> cnt(LANES);
-    for (int l = 0; l < LANES; ++l) cnt[l] = lane_sums(l, sl.n, s2, s3, cam, th2, Ki, c, g[l]);
-    std::vector<double> v(LANES * GRAM), nv(LANES * GRAM);
-    for (int l = 0; l < LANES; ++l)
-        for (int e = 0; e < GRAM; ++e) v[l * GRAM + e] = reinterpret_cast<const double *>(&g[l])[e];
-    for (int o = 1; o < 64; o <<= 1) { // v <- v + v[lane ^ o], within each wave
-        for (int l = 0; l < LANES; ++l)
-            for (int e = 0; e < GRAM; ++e) nv[l * GRAM + e] = v[l * GRAM + e] + v[(l ^ o) * GRAM + e];
-        v.swap(nv);
-    }
-    cvx::Gram total;
-    for (int e = 0; e < GRAM; ++e) reinterpret_cast<double *>(&total)[e] = waves_total(v.data(), 64 * GRAM, e); // lane 0 of each wave
-    int n = 0;
-    for (int l = 0; l < LANES; ++l) n += cnt[l];
-    double B[27], Q9[45];
-    const bool ok = finish(total, n, det, c, B, Q9);
-    for (int i = 0; i < 27; ++i) B27[ai * 27 + i] = ok ? B[i] : NAN;
-    for (int i = 0; i < 45; ++i) Q45[ai * 45 + i] = ok ? Q9[i] : NAN;
-    count[ai] = n;
+    cvxas::centre(nf, first, s3, c);
+    cvxas::assemble_entry(ai, c, det, [&](int l, cvx::Gram &g) { return lane_sums(l, sl.n, s2, s3, cam, th2, Ki, c, g); }, B27, Q45, count);
 }
 
 } // namespace
@@ -143,7 +112,7 @@ extern "C" int cvxpnpl_ransac_lo_assemble_host(int64_t n_scenes, int64_t n_activ
         for (int64_t ai = lo; ai < hi; ++ai) { // the kernel's workgroup
             const int64_t f = active[ai];
             if (f < 0 || f >= n_scenes) continue; // skipped, not clamped
-            assemble_entry(ai, f, offsets, n_total, scene_2d, scene_3d, R, t, K, K_per_scene, th2, B27, Q45, count);
+            host_entry(ai, f, offsets, n_total, scene_2d, scene_3d, R, t, K, K_per_scene, th2, B27, Q45, count);
         }
     });
     return 0;

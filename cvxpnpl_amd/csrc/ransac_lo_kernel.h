@@ -2,7 +2,7 @@
 // round every active scene's running best is refitted on its consensus set by the non-minimal solver, and the refitted pose's inlier
 // count drives the stopping rule.  Two kernels around the solve at the cost seam, both in the COMPACT layout of a round (entry a of the
 // active list; an entry outside [0, n_scenes) is skipped, not clamped) over the clamped slices of cvxn::scene_slice, and one that zeroes
-// the counter.  The rules are ransac_lo_core.h; the camera, the predicate and the mask of a pose are cvxn::camera_load, cvxn::is_inlier
+// the counter.  The rules are ransac_lo_core.h and ransac_assemble_core.h; the camera, the predicate and the mask of a pose are cvxn::camera_load, cvxn::is_inlier
 // and cvxn::block_inliers as they stand.  Every loop is bounded by M_f or a constant; nothing waits for another workgroup; no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -14,39 +14,9 @@
 
 namespace cvxnlo {
 
+using cvxas::wave_uniform;
 using cvxn::SCENE_BLOCK;
 using cvxn::SCENE_WAVES;
-
-// a value every lane of the wavefront holds, moved to the scalar registers: the camera, K^-1 and the centre are workgroup-uniform and
-// read in every iteration of the assembly loop, beside 60 running sums per lane
-__device__ inline double wave_uniform(double v)
-{
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-template <int N>
-__device__ inline void wave_uniform(double (&v)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = wave_uniform(v[i]);
-}
-
-__device__ inline double wave_xor_add(double v, int o) { return v + __shfl_xor(v, o); }
-
-// the 60 sums of a Gram to and from a flat array, by static indices (registers)
-__device__ inline void gram_store(const cvx::Gram &g, double *dst)
-{
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dst[i] = g.M0[i];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dst[6 + k * 6 + i] = g.M1[k][i];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dst[24 + k * 6 + i] = g.M2[k][i];
-}
 
 // ---- the assembly of a step: ONE workgroup of four wavefronts per active entry.  cvxn::assemble_consensus_kernel with the inlier
 // predicate in place of the mask: the correspondences that pass it at the scene's running pose (R[f], t[f]) under thresh_k are summed
@@ -113,46 +83,12 @@ __global__ void __launch_bounds__(LANES) lo_assemble_active_kernel(LoAssembleArg
         }
     }
     double c[3];
-    centre(nf, first, s3, c);
+    cvxas::centre(nf, first, s3, c);
     wave_uniform(c);
-    {
-        cvx::Gram g;
-        int n = lane_sums(tid, sl.n, s2, s3, cam, th2, Ki, c, g);
-#pragma unroll 1
-        for (int o = 1; o < 64; o <<= 1) { // (rolled: six passes over the same 60 sums)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g.M0[i] = wave_xor_add(g.M0[i], o);
-#pragma unroll
-            for (int k = 0; k < 3; ++k)
-#pragma unroll
-                for (int i = 0; i < 6; ++i) g.M1[k][i] = wave_xor_add(g.M1[k][i], o);
-#pragma unroll
-            for (int k = 0; k < 6; ++k)
-#pragma unroll
-                for (int i = 0; i < 6; ++i) g.M2[k][i] = wave_xor_add(g.M2[k][i], o);
-            n += __shfl_xor(n, o);
-        }
-        if (lane == 0) { // (every lane of the wave holds the wave's sums)
-            gram_store(g, part + wave * GRAM);
-            cnt_w[wave] = n;
-        }
-    }
-    __syncthreads();
-    if (tid < GRAM) total[tid] = waves_total(part, GRAM, tid);
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) n += cnt_w[w];
-    __syncthreads();
-    if (wave != 0) return; // (no barrier below)
-    double B[27], Q9[45];
-    const bool ok = finish(*reinterpret_cast<const cvx::Gram *>(total), n, det, c, B, Q9);
-    if (tid == 0) { // (every lane holds the same values; static indices keep B and Q9 in registers)
-#pragma unroll
-        for (int i = 0; i < 27; ++i) a.B27[ai * 27 + i] = ok ? B[i] : NAN;
-#pragma unroll
-        for (int i = 0; i < 45; ++i) a.Q45[ai * 45 + i] = ok ? Q9[i] : NAN;
-        a.count[ai] = n;
-    }
+    cvx::Gram g;
+    int n = lane_sums(tid, sl.n, s2, s3, cam, th2, Ki, c, g);
+    cvxas::wave_butterfly(g, n);
+    cvxas::block_finish_store(g, n, part, total, cnt_w, det, c, ai, a.B27, a.Q45, a.count);
 }
 
 // ---- the update of a step: ONE workgroup per active entry.  The refitted pose (fit_R, fit_t, fit_status)[a] is scored against scene
@@ -197,16 +133,8 @@ __global__ void __launch_bounds__(SCENE_BLOCK) lo_update_active_kernel(LoUpdateA
     const int n_new = cvxn::block_inliers(cam, sl.n, s2, s3, th2, nullptr, red);
     const bool take = take_fit(st, a.fit_cnt[ai], n_new, best_prev, head_prev); // (workgroup-uniform)
     __syncthreads();
-    if (take) {
-        (void)cvxn::block_inliers(cam, sl.n, s2, s3, th2, a.mask + sl.beg, red); // pose and mask change together
-        cvxn::take_pose(a.fit_R, a.fit_t, ai, a.io_R, a.io_t, f);
-        if (threadIdx.x == 0) {
-            a.head[f * 4] = st; a.head[f * 4 + 1] = n_new;
-            a.best[f] = n_new;
-            a.lo_taken[f] += 1;
-        }
-    }
-    if (threadIdx.x == 0 && cvxna::scene_done(a.hyp_used[f], a.cap, take ? n_new : best_prev, sl.n, a.confidence)) a.done[ai] = 1;
+    if (take) (void)cvxn::block_inliers(cam, sl.n, s2, s3, th2, a.mask + sl.beg, red); // pose and mask change together
+    commit_fit(take, st, n_new, best_prev, sl.n, a.fit_R, a.fit_t, ai, a.io_R, a.io_t, f, a.head, a.best, a.lo_taken, a.hyp_used, a.cap, a.confidence, a.done);
 }
 
 // ---- start of a call with local optimisation: lo_taken[f] = 0.  One lane per scene.

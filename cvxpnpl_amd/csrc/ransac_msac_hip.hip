@@ -11,20 +11,6 @@
 
 using namespace cvxne;
 
-namespace {
-
-// the pointers of a call that launches, each under its own name: the first null one becomes the message
-struct Named { const char *name; const void *p; };
-template <int N>
-int null_among(const char *who, const Named (&ptrs)[N])
-{
-    for (const Named &n : ptrs)
-        if (!n.p) return cvxee::fail(-1, "%s: bad arguments (%s is null)", who, n.name);
-    return 0;
-}
-
-} // namespace
-
 extern "C" const char *cvxpnpl_ransac_msac_last_error(void) { return err_buf(); }
 
 extern "C" int cvxpnpl_ransac_msac_score_scenes(int64_t n_scenes, int32_t n_hyp, const int64_t *d_offsets, int64_t n_total, const double *d_R,

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "ransac_assemble_core.h"
 #include "ransac_pnpl_common.h"
 
 namespace cvxnl {
@@ -105,7 +106,7 @@ __global__ void __launch_bounds__(BLOCK) select_kernel(SelectArgs a)
 
 // ---- consensus assembly: ONE wavefront per scene, cvxn::assemble_consensus_kernel over masked points, then masked lines.  The lanes
 // stride over the scene's correspondences, each with Gram sums of its own; the 60 sums meet in a fixed-order XOR butterfly, after which
-// every lane holds the same total: the result depends on the inputs only.  The centre is cvx::shift_centre of the first three selected
+// every lane holds the same total: the result depends on the inputs only.  The centre is cvxas::centre of the first three selected
 // 3D RECORDS in the order "points, then lines" (a line contributes its two end points): the centre cvxpnpl_assemble_batch uses on the
 // gathered set.  Fewer than three CORRESPONDENCES taken, a singular N^T N or a singular K: NaN for that scene only.
 struct ConsensusArgs {
@@ -114,27 +115,6 @@ struct ConsensusArgs {
     double *B27, *Q45;               // [n_scenes][27], [n_scenes][45]
     int32_t *count;                  // [n_scenes]
 };
-__device__ inline double wave_xor_add(double v, int o) { return v + __shfl_xor(v, o); }
-// positions of the first `want` (at most 3) set entries of mask[0 .. n), in order: ballots over chunks of 64 (wave-uniform)
-__device__ inline int first_selected(const uint8_t *mask, int n, int want, int *first)
-{
-    const int lane = threadIdx.x;
-    int nf = 0;
-    for (int64_t base = 0; base < n && nf < want; base += 64) {
-        const int64_t m = base + lane;
-        unsigned long long b = __ballot(m < n && mask[m] != 0);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            if (b != 0 && nf < want) {
-                const int pos = (int)base + __ffsll((long long)b) - 1; // (< n)
-                first[0] = nf == 0 ? pos : first[0]; first[1] = nf == 1 ? pos : first[1]; first[2] = nf == 2 ? pos : first[2];
-                ++nf;
-                b &= b - 1;
-            }
-        }
-    }
-    return nf;
-}
 __global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
 {
     const int64_t f = blockIdx.x;
@@ -148,26 +128,10 @@ __global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
     cvx::inv3(Kc, Ki, det);
     // the first three selected records: up to three points, then -- while fewer than three records -- up to two lines
     int fp[3] = {0, 0, 0}, fl[3] = {0, 0, 0};
-    const int nfp = first_selected(mp, sc.P, 3, fp);
-    const int nfl = nfp < 3 ? first_selected(ml, sc.L, nfp == 0 ? 2 : 1, fl) : 0;
-    const int nrec = nfp + 2 * nfl < 3 ? nfp + 2 * nfl : 3;
-    double c[3] = {0.0, 0.0, 0.0};
-    if (nrec > 0) {
-        double first3[9];
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { // (entries beyond nrec repeat the first record and are not read by shift_centre)
-            const int kk = k < nrec ? k : 0;
-            const double *r;
-            if (kk < nfp) {
-                r = sc.p3 + 3 * (int64_t)(kk == 0 ? fp[0] : (kk == 1 ? fp[1] : fp[2]));
-            } else {
-                const int e = kk - nfp; // end point e of the selected lines: line e / 2, end e % 2
-                r = sc.l3 + 6 * (int64_t)(e < 2 ? fl[0] : fl[1]) + 3 * (e & 1);
-            }
-            first3[3 * k] = r[0]; first3[3 * k + 1] = r[1]; first3[3 * k + 2] = r[2];
-        }
-        cvx::shift_centre(nrec, first3, 0, nullptr, c);
-    }
+    const int nfp = cvxas::wave_first(sc.P, 3, fp, [&](int64_t m) { return mp[m] != 0; });
+    const int nfl = cvxas::wave_first(sc.L, cvxas::centre_lines_wanted(nfp), fl, [&](int64_t m) { return ml[m] != 0; });
+    double c[3];
+    cvxas::centre(nfp, fp, nfl, fl, sc.p3, sc.l3, c);
     cvx::Gram g;
     cvx::gram_zero(g);
     int n = 0;
@@ -185,33 +149,10 @@ __global__ void __launch_bounds__(64) assemble_consensus_kernel(ConsensusArgs a)
         cvx::gram_add_line(g, Ki, ab, es);
         ++n;
     }
-#pragma unroll 1
-    for (int o = 1; o < 64; o <<= 1) { // (rolled: six passes over the same 60 sums)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) g.M0[i] = wave_xor_add(g.M0[i], o);
-#pragma unroll
-        for (int k = 0; k < 3; ++k)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g.M1[k][i] = wave_xor_add(g.M1[k][i], o);
-#pragma unroll
-        for (int k = 0; k < 6; ++k)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g.M2[k][i] = wave_xor_add(g.M2[k][i], o);
-        n += __shfl_xor(n, o);
-    }
+    cvxas::wave_butterfly(g, n);
     double B[27], Q9[45];
-    const bool ok = n >= 3 && cvx::gram_finish(g, B, Q9) && (det == det) && det != 0.0;
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) B[i * 9 + 3 * j + i] += c[j];
-    if (lane == 0) { // (every lane holds the same values; static indices keep B and Q9 in registers)
-#pragma unroll
-        for (int i = 0; i < 27; ++i) a.B27[f * 27 + i] = ok ? B[i] : NAN;
-#pragma unroll
-        for (int i = 0; i < 45; ++i) a.Q45[f * 45 + i] = ok ? Q9[i] : NAN;
-        a.count[f] = n;
-    }
+    const bool ok = cvxas::finish(g, n, det, c, B, Q9);
+    if (lane == 0) cvxas::store_cost(ok, B, Q9, n, f, a.B27, a.Q45, a.count); // (every lane holds the same values)
 }
 
 // ---- refit update: ONE workgroup per scene, the rule of cvxn::refit_update_scenes_kernel.  The refitted pose of the scene's consensus
@@ -241,8 +182,7 @@ __global__ void __launch_bounds__(BLOCK) refit_update_kernel(RefitArgs a)
     __syncthreads();
     if (!take) return;
     (void)block_inliers(cam, sc, a.thresh, a.mask_p + sc.beg_p, a.mask_l + sc.beg_l, red); // pose and masks change together
-    if (threadIdx.x < 9) a.io_R[f * 9 + threadIdx.x] = a.fit_R[f * 9 + threadIdx.x];
-    if (threadIdx.x < 3) a.io_t[f * 3 + threadIdx.x] = a.fit_t[f * 3 + threadIdx.x];
+    cvxn::take_pose(a.fit_R, a.fit_t, f, a.io_R, a.io_t, f);
     if (threadIdx.x == 0) { a.head[f * 4] = st; a.head[f * 4 + 1] = n_new; }
 }
 

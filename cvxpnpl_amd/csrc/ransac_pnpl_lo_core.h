@@ -1,16 +1,17 @@
 // ransac_pnpl_lo_core.h -- the rules of local optimisation in adaptive RANSAC over points AND lines
 // (include/cvxpnpl_amd_ransac_pnpl_lo.h), ONE statement of them for the device (lo_assemble_pnpl_active_kernel,
 // lo_update_pnpl_active_kernel) and the host (cvxpnpl_ransac_pnpl_lo_assemble_host).  What section 24 states for points -- the camera, the
-// point predicate, the order of the wave sums, the finish and take_fit -- is ransac_lo_core.h as it stands; here is what lines add.
+// point predicate and take_fit -- is ransac_lo_core.h as it stands, the centre, the order of the sums and the finish are
+// ransac_assemble_core.h; here is what lines add.
 //
 // The assembly of one active entry, by LANES = 256 lanes in four wavefronts:
 //   taken point m = cvxn::is_inlier at the scene's running pose, threshold (thresh * m_k)^2                      (cvxnlo::taken)
 //   taken line m  = cvxnl::is_line_inlier, threshold thresh * m_k: the image line normalised ONCE, then both end points in front of the
 //                   camera and within the threshold of it                                                         (line_taken)
-//   centre        = cvx::shift_centre of the first three taken 3D RECORDS in the order "points, then lines", a line giving its two end
-//                   points: up to three points, then -- while fewer than three records -- up to two lines        (centre)
+//   centre        = cvxas::centre of the first three taken 3D RECORDS in the order "points, then lines", a line giving its two end
+//                   points: up to three points, then -- while fewer than three records -- cvxas::centre_lines_wanted lines
 //   lane l        adds its taken points l, l + 256, ... and then its taken lines l, l + 256, ... into the same 60 sums  (lane_sums)
-//   a wave, the entry: the XOR butterfly and the wave order of ransac_lo_core.h
+//   a wave, the entry: the XOR butterfly and the wave order of ransac_assemble_core.h
 // so the 60 sums depend on the inputs alone.  On the device the scene and the line predicate ARE cvxnl::scene_of and cvxnl::is_line_inlier;
 // those are device-only, so the host build restates them expression by expression (as ransac_lo_core.h does for the point predicate).
 #pragma once
@@ -73,33 +74,6 @@ __host__ __device__ inline bool line_taken(const cvxn::Camera &c, const double *
     const double l[3] = {l0 * inv, l1 * inv, lc * inv};
     return host_end_point_near(c, l, es[0], es[1], es[2], th) && host_end_point_near(c, l, es[3], es[4], es[5], th);
 #endif
-}
-
-// ---- how many lines the centre reads after nfp <= 3 taken points: none after three, one after one or two, two after none
-__host__ __device__ inline int centre_lines_wanted(int nfp) { return nfp >= 3 ? 0 : (nfp == 0 ? 2 : 1); }
-
-// ---- the centre: cvx::shift_centre of the first three taken records, the nfp <= 3 first taken points fp[0 .. nfp) and then the end
-// points of the nfl <= 2 first taken lines fl[0 .. nfl) (scene order); nothing taken: the origin.  The rule of
-// cvxnl::assemble_consensus_kernel.
-__host__ __device__ inline void centre(int nfp, const int *fp, int nfl, const int *fl, const double *p3, const double *l3, double *c)
-{
-    c[0] = c[1] = c[2] = 0.0;
-    const int nrec = nfp + 2 * nfl < 3 ? nfp + 2 * nfl : 3;
-    if (nrec <= 0) return;
-    double first3[9];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { // (entries beyond nrec repeat the first record and are not read by shift_centre)
-        const int kk = k < nrec ? k : 0;
-        const double *r;
-        if (kk < nfp) {
-            r = p3 + 3 * (int64_t)(kk == 0 ? fp[0] : (kk == 1 ? fp[1] : fp[2]));
-        } else {
-            const int e = kk - nfp; // end point e of the taken lines: line e / 2, end e % 2
-            r = l3 + 6 * (int64_t)(e < 2 ? fl[0] : fl[1]) + 3 * (e & 1);
-        }
-        first3[3 * k] = r[0]; first3[3 * k + 1] = r[1]; first3[3 * k + 2] = r[2];
-    }
-    cvx::shift_centre(nrec, first3, 0, nullptr, c);
 }
 
 // ---- T = n n^T (packed 00 01 02 11 12 22) of a 2D line, n the normalised cross product of its two back-projected samples: the first half

@@ -5,8 +5,6 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#include <vector>
-
 #include "../../include/cvxpnpl_amd_ransac_pnpl_lo.h"
 #include "host_pool.h"
 #include "ransac_entry.h"
@@ -15,16 +13,6 @@
 using namespace cvxne;
 
 namespace {
-
-// the pointers of a call that launches, each under its own name: the first null one becomes the message
-struct Named { const char *name; const void *p; };
-template <int N>
-int null_among(const char *who, const Named (&ptrs)[N])
-{
-    for (const Named &n : ptrs)
-        if (!n.p) return cvxee::fail(-1, "%s: bad arguments (%s is null)", who, n.name);
-    return 0;
-}
 
 // The sizes of a round and -- a call that does something -- its active list and scene set, every pointer under its own name (pre: "d_"
 // for a device entry point, "" for the host's); fills s, K left to the entry point.
@@ -42,8 +30,8 @@ int check_round_named(const char *who, const char *pre, int64_t n_scenes, int64_
     return 0;
 }
 
-// one entry of the host assembly: the lanes, the butterflies and the wave order of lo_assemble_pnpl_active_kernel, serially
-void assemble_entry(int64_t ai, int64_t f, const cvxnl::SceneSet &s, const double *R, const double *t, double th, double *B27, double *Q45, int32_t *count)
+// one entry of the host assembly: the first-three scans and the lanes of lo_assemble_pnpl_active_kernel, the rest cvxas::assemble_entry
+void host_entry(int64_t ai, int64_t f, const cvxnl::SceneSet &s, const double *R, const double *t, double th, double *B27, double *Q45, int32_t *count)
 {
     using namespace cvxnllo;
     const cvxnl::Scene sc = scene(s, f);
@@ -55,31 +43,12 @@ void assemble_entry(int64_t ai, int64_t f, const cvxnl::SceneSet &s, const doubl
     int fp[3] = {0, 0, 0}, fl[3] = {0, 0, 0}, nfp = 0, nfl = 0;
     for (int64_t m = 0; m < sc.P && nfp < 3; ++m)
         if (cvxnlo::taken(cam, sc.p2, sc.p3, m, th2)) fp[nfp++] = (int)m;
-    const int want = centre_lines_wanted(nfp);
+    const int want = cvxas::centre_lines_wanted(nfp);
     for (int64_t m = 0; m < sc.L && nfl < want; ++m)
         if (line_taken(cam, sc.l2, sc.l3, m, th)) fl[nfl++] = (int)m;
     double c[3];
-    centre(nfp, fp, nfl, fl, sc.p3, sc.l3, c);
-    std::vector<cvx::Gram> g(LANES);
-    std::vector<int> cnt(LANES);
-    for (int l = 0; l < LANES; ++l) cnt[l] = lane_sums(l, sc, cam, th, th2, Ki, c, g[l]);
-    std::vector<double> v(LANES * GRAM), nv(LANES * GRAM);
-    for (int l = 0; l < LANES; ++l)
-        for (int e = 0; e < GRAM; ++e) v[l * GRAM + e] = reinterpret_cast<const double *>(&g[l])[e];
-    for (int o = 1; o < 64; o <<= 1) { // v <- v + v[lane ^ o], within each wave
-        for (int l = 0; l < LANES; ++l)
-            for (int e = 0; e < GRAM; ++e) nv[l * GRAM + e] = v[l * GRAM + e] + v[(l ^ o) * GRAM + e];
-        v.swap(nv);
-    }
-    cvx::Gram total;
-    for (int e = 0; e < GRAM; ++e) reinterpret_cast<double *>(&total)[e] = cvxnlo::waves_total(v.data(), 64 * GRAM, e); // lane 0 of each wave
-    int n = 0;
-    for (int l = 0; l < LANES; ++l) n += cnt[l];
-    double B[27], Q9[45];
-    const bool ok = cvxnlo::finish(total, n, det, c, B, Q9);
-    for (int i = 0; i < 27; ++i) B27[ai * 27 + i] = ok ? B[i] : NAN;
-    for (int i = 0; i < 45; ++i) Q45[ai * 45 + i] = ok ? Q9[i] : NAN;
-    count[ai] = n;
+    cvxas::centre(nfp, fp, nfl, fl, sc.p3, sc.l3, c);
+    cvxas::assemble_entry(ai, c, det, [&](int l, cvx::Gram &g) { return lane_sums(l, sc, cam, th, th2, Ki, c, g); }, B27, Q45, count);
 }
 
 } // namespace
@@ -155,7 +124,7 @@ extern "C" int cvxpnpl_ransac_pnpl_lo_assemble_host(int64_t n_scenes, int64_t n_
         for (int64_t ai = lo; ai < hi; ++ai) { // the kernel's workgroup
             const int64_t f = active[ai];
             if (f < 0 || f >= n_scenes) continue; // skipped, not clamped
-            assemble_entry(ai, f, s, R, t, thresh_k, B27, Q45, count);
+            host_entry(ai, f, s, R, t, thresh_k, B27, Q45, count);
         }
     });
     return 0;

@@ -2,9 +2,9 @@
 // section 25): at the end of a round every active scene's running best is refitted on the points and lines within the step's threshold
 // of it, and the refitted pose's inlier count -- points plus lines -- drives the stopping rule.  Two kernels around the solve at the cost
 // seam, both in the COMPACT layout of a round (entry a of the active list; an entry outside [0, n_scenes) is skipped, not clamped) over
-// the clamped slices of cvxnl::scene_of.  The rules are ransac_pnpl_lo_core.h and ransac_lo_core.h; the camera, the predicates and the
-// masks of a pose are cvxn::camera_load, cvxn::is_inlier, cvxnl::is_line_inlier and cvxnl::block_inliers as they stand.  Every loop is
-// bounded by P_f, L_f or a constant; nothing waits for another workgroup; no atomics.
+// the clamped slices of cvxnl::scene_of.  The rules are ransac_pnpl_lo_core.h, ransac_lo_core.h and ransac_assemble_core.h; the camera,
+// the predicates and the masks of a pose are cvxn::camera_load, cvxn::is_inlier, cvxnl::is_line_inlier and cvxnl::block_inliers as they
+// stand.  Every loop is bounded by P_f, L_f or a constant; nothing waits for another workgroup; no atomics.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,41 +17,11 @@
 
 namespace cvxnllo {
 
+using cvxas::wave_uniform;
 using cvxn::SCENE_BLOCK;
 using cvxn::SCENE_WAVES;
 using cvxnl::Scene;
 using cvxnl::SceneSet;
-
-// a value every lane of the wavefront holds, moved to the scalar registers: the camera, K^-1 and the centre are workgroup-uniform and
-// read in every iteration of the assembly loops, beside 60 running sums per lane
-__device__ inline double wave_uniform(double v)
-{
-    const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v)), hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-    return __hiloint2double(hi, lo);
-}
-template <int N>
-__device__ inline void wave_uniform(double (&v)[N])
-{
-#pragma unroll
-    for (int i = 0; i < N; ++i) v[i] = wave_uniform(v[i]);
-}
-
-__device__ inline double wave_xor_add(double v, int o) { return v + __shfl_xor(v, o); }
-
-// the 60 sums of a Gram to a flat array, by static indices (registers)
-__device__ inline void gram_store(const cvx::Gram &g, double *dst)
-{
-#pragma unroll
-    for (int i = 0; i < 6; ++i) dst[i] = g.M0[i];
-#pragma unroll
-    for (int k = 0; k < 3; ++k)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dst[6 + k * 6 + i] = g.M1[k][i];
-#pragma unroll
-    for (int k = 0; k < 6; ++k)
-#pragma unroll
-        for (int i = 0; i < 6; ++i) dst[24 + k * 6 + i] = g.M2[k][i];
-}
 
 // positions of the first `want` (at most 3) of n correspondences that pass pred(m), in scene order, by chunks of LANES: a wavefront
 // ballots its 64 lanes, the four ballots meet in LDS, and a taken correspondence whose rank -- those found in earlier chunks, the
@@ -113,7 +83,7 @@ __global__ void __launch_bounds__(LANES) lo_assemble_pnpl_active_kernel(LoAssemb
     if (ai >= a.n_active) return;
     const int64_t f = a.active[ai];
     if (f < 0 || f >= a.s.n_scenes) return; // (block-uniform) skipped, not clamped
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const Scene sc = scene(a.s, f);
     cvxn::Camera cam;
     cvxnlo::camera(a.R + f * 9, a.t + f * 3, sc.K, cam);
@@ -124,58 +94,19 @@ __global__ void __launch_bounds__(LANES) lo_assemble_pnpl_active_kernel(LoAssemb
     // the first three taken records: up to three points, then -- while fewer than three records -- up to two lines (block-uniform)
     int fp[3] = {0, 0, 0}, fl[3] = {0, 0, 0};
     const int nfp = first_taken(sc.P, 3, fp, ballot_w, slot, [&](int64_t m) { return cvxnlo::taken(cam, sc.p2, sc.p3, m, th2); });
-    const int nfl = first_taken(sc.L, centre_lines_wanted(nfp), fl, ballot_w, slot, [&](int64_t m) { return line_taken(cam, sc.l2, sc.l3, m, th); });
+    const int nfl = first_taken(sc.L, cvxas::centre_lines_wanted(nfp), fl, ballot_w, slot, [&](int64_t m) { return line_taken(cam, sc.l2, sc.l3, m, th); });
     double c[3];
-    centre(nfp, fp, nfl, fl, sc.p3, sc.l3, c);
+    cvxas::centre(nfp, fp, nfl, fl, sc.p3, sc.l3, c);
     wave_uniform(c);
     double Kc[9], Ki[9], det; // (K^-1 only now: the search above holds enough in scalar registers without it)
 #pragma unroll
     for (int i = 0; i < 9; ++i) Kc[i] = sc.K[i];
     cvx::inv3(Kc, Ki, det);
     wave_uniform(Ki);
-    {
-        cvx::Gram g;
-        int n = lane_sums(tid, sc, cam, th, th2, Ki, c, g);
-#pragma unroll 1
-        for (int o = 1; o < 64; o <<= 1) { // (rolled: six passes over the same 60 sums; in groups of twelve, so that the exchanged
-                                           // values of a pass are never all in flight beside the sums)
-#pragma unroll
-            for (int i = 0; i < 6; ++i) g.M0[i] = wave_xor_add(g.M0[i], o);
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) g.M1[k][i] = wave_xor_add(g.M1[k][i], o);
-                if (k != 1) __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int k = 0; k < 6; ++k) {
-#pragma unroll
-                for (int i = 0; i < 6; ++i) g.M2[k][i] = wave_xor_add(g.M2[k][i], o);
-                if (k & 1) __builtin_amdgcn_sched_barrier(0);
-            }
-            n += __shfl_xor(n, o);
-        }
-        if (lane == 0) { // (every lane of the wave holds the wave's sums)
-            gram_store(g, part + wave * GRAM);
-            cnt_w[wave] = n;
-        }
-    }
-    __syncthreads();
-    if (tid < GRAM) total[tid] = cvxnlo::waves_total(part, GRAM, tid);
-    int n = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) n += cnt_w[w];
-    __syncthreads();
-    if (wave != 0) return; // (no barrier below)
-    double B[27], Q9[45];
-    const bool ok = cvxnlo::finish(*reinterpret_cast<const cvx::Gram *>(total), n, det, c, B, Q9);
-    if (tid == 0) { // (every lane holds the same values; static indices keep B and Q9 in registers)
-#pragma unroll
-        for (int i = 0; i < 27; ++i) a.B27[ai * 27 + i] = ok ? B[i] : NAN;
-#pragma unroll
-        for (int i = 0; i < 45; ++i) a.Q45[ai * 45 + i] = ok ? Q9[i] : NAN;
-        a.count[ai] = n;
-    }
+    cvx::Gram g;
+    int n = lane_sums(tid, sc, cam, th, th2, Ki, c, g);
+    cvxas::wave_butterfly(g, n);
+    cvxas::block_finish_store(g, n, part, total, cnt_w, det, c, ai, a.B27, a.Q45, a.count);
 }
 
 // ---- the update of a step: ONE workgroup per active entry, cvxnlo::lo_update_active_kernel over a cvxnl::Scene.  The refitted pose
@@ -216,16 +147,9 @@ __global__ void __launch_bounds__(SCENE_BLOCK) lo_update_pnpl_active_kernel(LoUp
     const int n_new = cvxnl::block_inliers(cam, sc, a.thresh, nullptr, nullptr, red);
     const bool take = cvxnlo::take_fit(st, a.fit_cnt[ai], n_new, best_prev, head_prev); // (workgroup-uniform)
     __syncthreads();
-    if (take) {
-        (void)cvxnl::block_inliers(cam, sc, a.thresh, a.mask_p + sc.beg_p, a.mask_l + sc.beg_l, red); // pose and masks change together
-        cvxn::take_pose(a.fit_R, a.fit_t, ai, a.io_R, a.io_t, f);
-        if (threadIdx.x == 0) {
-            a.head[f * 4] = st; a.head[f * 4 + 1] = n_new;
-            a.best[f] = n_new;
-            a.lo_taken[f] += 1;
-        }
-    }
-    if (threadIdx.x == 0 && cvxna::scene_done(a.hyp_used[f], a.cap, take ? n_new : best_prev, sc.P + sc.L, a.confidence)) a.done[ai] = 1;
+    if (take) (void)cvxnl::block_inliers(cam, sc, a.thresh, a.mask_p + sc.beg_p, a.mask_l + sc.beg_l, red); // pose and masks change together
+    cvxnlo::commit_fit(take, st, n_new, best_prev, sc.P + sc.L, a.fit_R, a.fit_t, ai, a.io_R, a.io_t, f, a.head, a.best, a.lo_taken, a.hyp_used, a.cap,
+                       a.confidence, a.done);
 }
 
 } // namespace cvxnllo

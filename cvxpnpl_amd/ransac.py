@@ -490,6 +490,66 @@ def _check_local_opt(local_opt, lo_widen, confidence, scoring):
     return n, w
 
 
+def _lo_cost_out(out, A, dev):
+    """The (B27 [A,27], Q45 [A,45], cnt [A] int32) an LO assembly writes: allocated, or the caller's three tensors checked."""
+    if out is None:
+        out = (torch.empty((A, 27), dtype=torch.float64, device=dev), torch.empty((A, 45), dtype=torch.float64, device=dev),
+               torch.empty((A,), dtype=torch.int32, device=dev))
+    Bt, Qt, cnt = out
+    _chk(Bt, "out B27", torch.float64, (A, 27), dev)
+    _chk(Qt, "out Q45", torch.float64, (A, 45), dev)
+    _chk(cnt, "out cnt", torch.int32, (A,), dev)
+    return Bt, Qt, cnt
+
+
+def _lo_update_args(sc, st, n_active, cap, confidence, fit, cnt):
+    """What an LO update checks after its scenes and state: lo_taken, confidence, the active list, cap, the fit and its counts.
+    Returns (A, cap, confidence)."""
+    if getattr(st, "lo_taken", None) is None:
+        raise ValueError("state.lo_taken is missing: the state of a call with local optimisation goes through lo_init")
+    dev = sc.device
+    _chk(st.lo_taken, "state.lo_taken", torch.int32, (sc.F,), dev)
+    conf, _ = _check_adaptive(confidence, 1)
+    A = _chk_active(sc, st.active, n_active)
+    cp = int(cap)
+    if not 0 <= cp <= 0x7FFFFFFF:
+        raise ValueError(f"cap must be an int >= 0 (and below 2^31), got {cap!r}")
+    _chk(fit.R, "fit.R", torch.float64, (A, 3, 3), dev)
+    _chk(fit.t, "fit.t", torch.float64, (A, 3), dev)
+    _chk(fit.status, "fit.status", torch.int32, (A,), dev)
+    _chk(cnt, "cnt", torch.int32, (A,), dev)
+    return A, cp, conf
+
+
+def _lo_assemble_host(lib, name, F, K, R, t, active, scenes_wrong, call):
+    """What the two host assemblies share once the packed scenes are arrays: K, R, t and active converted, then scenes_wrong (the
+    scene-shape message, or None) and their own shapes checked in that order; the NaN / -1 outputs; call(L, ptr, act, R, t, K, B27, Q45,
+    cnt) -> the return code of the entry point of L = lib(), ptr mapping an array to its pointer (None for an empty one); the raise on a
+    failure."""
+    import ctypes as C
+
+    Kh = _np.ascontiguousarray(K, dtype=_np.float64)
+    Rh = _np.ascontiguousarray(R, dtype=_np.float64)
+    th = _np.ascontiguousarray(t, dtype=_np.float64)
+    act = _np.ascontiguousarray(active, dtype=_np.int32)
+    if scenes_wrong:
+        raise ValueError(scenes_wrong)
+    if Kh.shape != (3, 3) and Kh.shape != (F, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{F},3,3], got {Kh.shape}")
+    if Rh.shape != (F, 3, 3) or th.shape != (F, 3):
+        raise ValueError(f"R must be [{F},3,3] and t [{F},3], got {Rh.shape} and {th.shape}")
+    if act.ndim != 1:
+        raise ValueError(f"active must have one dimension, got shape {act.shape}")
+    A = act.shape[0]
+    Bt, Qt, cnt = _np.full((A, 27), _np.nan), _np.full((A, 45), _np.nan), _np.full(A, -1, dtype=_np.int32)
+    ptr = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)  # noqa: E731
+    L = lib()
+    rc = call(L, ptr, act, Rh, th, Kh, Bt, Qt, cnt)
+    if rc != 0:
+        raise RuntimeError(f"{name}_assemble_host failed ({rc}): {getattr(L, name + '_last_error')().decode()}")
+    return Bt, Qt, cnt
+
+
 def lo_init(sc: Scenes, st: AdaptiveState) -> AdaptiveState:
     """cvxpnpl_ransac_lo_init: st.lo_taken [F] int32 = 0, the refits taken per scene.  Returns st."""
     _require_gpu()
@@ -510,13 +570,7 @@ def lo_assemble_active(sc: Scenes, st: AdaptiveState, n_active: int, thresh_k: f
     _chk_scenes(sc)
     _chk_state(sc, st)
     A, dev = _chk_active(sc, st.active, n_active), sc.device
-    if out is None:
-        out = (torch.empty((A, 27), dtype=torch.float64, device=dev), torch.empty((A, 45), dtype=torch.float64, device=dev),
-               torch.empty((A,), dtype=torch.int32, device=dev))
-    Bt, Qt, cnt = out
-    _chk(Bt, "out B27", torch.float64, (A, 27), dev)
-    _chk(Qt, "out Q45", torch.float64, (A, 45), dev)
-    _chk(cnt, "out cnt", torch.int32, (A,), dev)
+    Bt, Qt, cnt = _lo_cost_out(out, A, dev)
     _call("ransac_lo", sc, "cvxpnpl_ransac_lo_assemble", sc.F, A, _ptr(st.active), _ptr(sc.offsets), sc.total, _ptr(sc.x), _ptr(sc.X), _ptr(st.R), _ptr(st.t),
           _ptr(sc.K), sc.per_scene_K, float(thresh_k), _ptr(Bt), _ptr(Qt), _ptr(cnt))
     return Bt, Qt, cnt
@@ -531,19 +585,7 @@ def lo_update_active(sc: Scenes, st: AdaptiveState, n_active: int, cap: int, con
     _require_gpu()
     _chk_scenes(sc)
     _chk_state(sc, st)
-    if getattr(st, "lo_taken", None) is None:
-        raise ValueError("state.lo_taken is missing: the state of a call with local optimisation goes through lo_init")
-    dev = sc.device
-    _chk(st.lo_taken, "state.lo_taken", torch.int32, (sc.F,), dev)
-    conf, _ = _check_adaptive(confidence, 1)
-    A = _chk_active(sc, st.active, n_active)
-    cp = int(cap)
-    if not 0 <= cp <= 0x7FFFFFFF:
-        raise ValueError(f"cap must be an int >= 0 (and below 2^31), got {cap!r}")
-    _chk(fit.R, "fit.R", torch.float64, (A, 3, 3), dev)
-    _chk(fit.t, "fit.t", torch.float64, (A, 3), dev)
-    _chk(fit.status, "fit.status", torch.int32, (A,), dev)
-    _chk(cnt, "cnt", torch.int32, (A,), dev)
+    A, cp, conf = _lo_update_args(sc, st, n_active, cap, confidence, fit, cnt)
     _call("ransac_lo", sc, "cvxpnpl_ransac_lo_update", sc.F, A, _ptr(st.active), cp, conf, _ptr(sc.offsets), sc.total, _ptr(fit.R), _ptr(fit.t),
           _ptr(fit.status), _ptr(cnt), _ptr(sc.K), sc.per_scene_K, _ptr(sc.x), _ptr(sc.X), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
           _ptr(st.best), _ptr(st.mask), _ptr(st.hyp_used), _ptr(st.lo_taken), _ptr(st.done))
@@ -554,37 +596,20 @@ def lo_assemble_host(scene_2d, scene_3d, sizes, K, R, t, active, thresh_k: float
     the same order of the sums).  scene_2d [sum M,2], scene_3d [sum M,3] packed with sizes (F ints), K [3,3] or [F,3,3], R [F,3,3], t [F,3]
     the running poses, active: A scene indices.  Returns numpy (B27 [A,27], Q45 [A,45], cnt [A] int32); the rows of an entry outside
     [0, F) keep their initial NaN / -1.  No GPU needed."""
-    import ctypes as C
-
     szs = [int(m) for m in sizes]
     F, total = len(szs), sum(szs)
     if F < 1 or any(m < 0 for m in szs):
         raise ValueError("sizes: at least one scene, no negative size")
     x = _np.ascontiguousarray(scene_2d, dtype=_np.float64)
     X = _np.ascontiguousarray(scene_3d, dtype=_np.float64)
-    Kh = _np.ascontiguousarray(K, dtype=_np.float64)
-    Rh = _np.ascontiguousarray(R, dtype=_np.float64)
-    th = _np.ascontiguousarray(t, dtype=_np.float64)
-    act = _np.ascontiguousarray(active, dtype=_np.int32)
+    wrong = None
     if x.shape != (total, 2) or X.shape != (total, 3):
-        raise ValueError(f"packed scenes: expected [{total},2] and [{total},3], got {x.shape} and {X.shape}")
-    if Kh.shape != (3, 3) and Kh.shape != (F, 3, 3):
-        raise ValueError(f"K must be [3,3] or [{F},3,3], got {Kh.shape}")
-    if Rh.shape != (F, 3, 3) or th.shape != (F, 3):
-        raise ValueError(f"R must be [{F},3,3] and t [{F},3], got {Rh.shape} and {th.shape}")
-    if act.ndim != 1:
-        raise ValueError(f"active must have one dimension, got shape {act.shape}")
-    A = act.shape[0]
+        wrong = f"packed scenes: expected [{total},2] and [{total},3], got {x.shape} and {X.shape}"
     off = _np.zeros(F + 1, dtype=_np.int64)
     _np.cumsum(szs, out=off[1:])
-    Bt, Qt, cnt = _np.full((A, 27), _np.nan), _np.full((A, 45), _np.nan), _np.full(A, -1, dtype=_np.int32)
-    L = _lib.ransac_lo_lib()
-    ptr = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)  # noqa: E731
-    rc = L.cvxpnpl_ransac_lo_assemble_host(F, A, ptr(act), ptr(off), total, ptr(x), ptr(X), ptr(Rh), ptr(th), ptr(Kh), int(Kh.ndim == 3), float(thresh_k),
-                                           ptr(Bt), ptr(Qt), ptr(cnt), int(n_threads))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_ransac_lo_assemble_host failed ({rc}): {L.cvxpnpl_ransac_lo_last_error().decode()}")
-    return Bt, Qt, cnt
+    return _lo_assemble_host(_lib.ransac_lo_lib, "cvxpnpl_ransac_lo", F, K, R, t, active, wrong, lambda L, ptr, act, Rh, th, Kh, Bt, Qt, cnt:
+                             L.cvxpnpl_ransac_lo_assemble_host(F, act.shape[0], ptr(act), ptr(off), total, ptr(x), ptr(X), ptr(Rh), ptr(th), ptr(Kh),
+                                                               int(Kh.ndim == 3), float(thresh_k), ptr(Bt), ptr(Qt), ptr(cnt), int(n_threads)))
 
 
 # ---- guided sampling: the best-ranked correspondences first (include/cvxpnpl_amd_ransac_guided.h, DESIGN.md section 20) ----------------
@@ -1206,13 +1231,7 @@ def lo_assemble_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, th
     _chk_pnpl_scenes(sc)
     _chk_pnpl_lo_state(sc, st)
     A, dev = _chk_active(sc, st.active, n_active), sc.device
-    if out is None:
-        out = (torch.empty((A, 27), dtype=torch.float64, device=dev), torch.empty((A, 45), dtype=torch.float64, device=dev),
-               torch.empty((A,), dtype=torch.int32, device=dev))
-    Bt, Qt, cnt = out
-    _chk(Bt, "out B27", torch.float64, (A, 27), dev)
-    _chk(Qt, "out Q45", torch.float64, (A, 45), dev)
-    _chk(cnt, "out cnt", torch.int32, (A,), dev)
+    Bt, Qt, cnt = _lo_cost_out(out, A, dev)
     _call("ransac_pnpl_lo", sc, "cvxpnpl_ransac_pnpl_lo_assemble", sc.F, A, _ptr(st.active), *_scene_args(sc), *_data_args(sc), _ptr(st.R), _ptr(st.t),
           _ptr(sc.K), sc.per_scene_K, float(thresh_k), _ptr(Bt), _ptr(Qt), _ptr(cnt))
     return Bt, Qt, cnt
@@ -1228,19 +1247,7 @@ def lo_update_pnpl_active(sc: PnplScenes, st: AdaptiveState, n_active: int, cap:
     _require_gpu()
     _chk_pnpl_scenes(sc)
     _chk_pnpl_lo_state(sc, st)
-    if getattr(st, "lo_taken", None) is None:
-        raise ValueError("state.lo_taken is missing: the state of a call with local optimisation goes through lo_init")
-    dev = sc.device
-    _chk(st.lo_taken, "state.lo_taken", torch.int32, (sc.F,), dev)
-    conf, _ = _check_adaptive(confidence, 1)
-    A = _chk_active(sc, st.active, n_active)
-    cp = int(cap)
-    if not 0 <= cp <= 0x7FFFFFFF:
-        raise ValueError(f"cap must be an int >= 0 (and below 2^31), got {cap!r}")
-    _chk(fit.R, "fit.R", torch.float64, (A, 3, 3), dev)
-    _chk(fit.t, "fit.t", torch.float64, (A, 3), dev)
-    _chk(fit.status, "fit.status", torch.int32, (A,), dev)
-    _chk(cnt, "cnt", torch.int32, (A,), dev)
+    A, cp, conf = _lo_update_args(sc, st, n_active, cap, confidence, fit, cnt)
     _call("ransac_pnpl_lo", sc, "cvxpnpl_ransac_pnpl_lo_update", sc.F, A, _ptr(st.active), cp, conf, *_scene_args(sc), _ptr(fit.R), _ptr(fit.t),
           _ptr(fit.status), _ptr(cnt), _ptr(sc.K), sc.per_scene_K, *_data_args(sc), float(thresh), _ptr(st.R), _ptr(st.t), _ptr(st.head),
           _ptr(st.best), _ptr(st.mask), _ptr(st.mask_lines), _ptr(st.hyp_used), _ptr(st.lo_taken), _ptr(st.done))
@@ -1252,8 +1259,6 @@ def lo_assemble_pnpl_host(pts_2d, pts_3d, line_2d, line_3d, sizes, line_sizes, K
     [sum L,2,3] packed with line_sizes (F ints each; a half may be None or empty), K [3,3] or [F,3,3], R [F,3,3], t [F,3] the running
     poses, active: A scene indices.  Returns numpy (B27 [A,27], Q45 [A,45], cnt [A] int32); the rows of an entry outside [0, F) keep
     their initial NaN / -1.  No GPU needed."""
-    import ctypes as C
-
     ps, ls = [int(m) for m in sizes], [int(m) for m in line_sizes]
     F, nP, nL = len(ps), sum(ps), sum(ls)
     if F < 1 or len(ls) != F or any(m < 0 for m in ps + ls):
@@ -1262,32 +1267,18 @@ def lo_assemble_pnpl_host(pts_2d, pts_3d, line_2d, line_3d, sizes, line_sizes, K
     X = _np.ascontiguousarray(_np.zeros((0, 3)) if pts_3d is None else pts_3d, dtype=_np.float64).reshape(-1, 3)
     l2 = _np.ascontiguousarray(_np.zeros((0, 2, 2)) if line_2d is None else line_2d, dtype=_np.float64).reshape(-1, 2, 2)
     l3 = _np.ascontiguousarray(_np.zeros((0, 2, 3)) if line_3d is None else line_3d, dtype=_np.float64).reshape(-1, 2, 3)
-    Kh = _np.ascontiguousarray(K, dtype=_np.float64)
-    Rh = _np.ascontiguousarray(R, dtype=_np.float64)
-    th = _np.ascontiguousarray(t, dtype=_np.float64)
-    act = _np.ascontiguousarray(active, dtype=_np.int32)
+    wrong = None
     if x.shape[0] != nP or X.shape[0] != nP:
-        raise ValueError(f"packed points: expected [{nP},2] and [{nP},3], got {x.shape} and {X.shape}")
-    if l2.shape[0] != nL or l3.shape[0] != nL:
-        raise ValueError(f"packed lines: expected [{nL},2,2] and [{nL},2,3], got {l2.shape} and {l3.shape}")
-    if Kh.shape != (3, 3) and Kh.shape != (F, 3, 3):
-        raise ValueError(f"K must be [3,3] or [{F},3,3], got {Kh.shape}")
-    if Rh.shape != (F, 3, 3) or th.shape != (F, 3):
-        raise ValueError(f"R must be [{F},3,3] and t [{F},3], got {Rh.shape} and {th.shape}")
-    if act.ndim != 1:
-        raise ValueError(f"active must have one dimension, got shape {act.shape}")
-    A = act.shape[0]
+        wrong = f"packed points: expected [{nP},2] and [{nP},3], got {x.shape} and {X.shape}"
+    elif l2.shape[0] != nL or l3.shape[0] != nL:
+        wrong = f"packed lines: expected [{nL},2,2] and [{nL},2,3], got {l2.shape} and {l3.shape}"
     off_p, off_l = _np.zeros(F + 1, dtype=_np.int64), _np.zeros(F + 1, dtype=_np.int64)
     _np.cumsum(ps, out=off_p[1:])
     _np.cumsum(ls, out=off_l[1:])
-    Bt, Qt, cnt = _np.full((A, 27), _np.nan), _np.full((A, 45), _np.nan), _np.full(A, -1, dtype=_np.int32)
-    L = _lib.ransac_pnpl_lo_lib()
-    ptr = lambda a: None if a is None or a.size == 0 else C.c_void_p(a.ctypes.data)  # noqa: E731
-    rc = L.cvxpnpl_ransac_pnpl_lo_assemble_host(F, A, ptr(act), ptr(off_p), nP, ptr(off_l), nL, ptr(x), ptr(X), ptr(l2), ptr(l3), ptr(Rh), ptr(th), ptr(Kh),
-                                                int(Kh.ndim == 3), float(thresh_k), ptr(Bt), ptr(Qt), ptr(cnt), int(n_threads))
-    if rc != 0:
-        raise RuntimeError(f"cvxpnpl_ransac_pnpl_lo_assemble_host failed ({rc}): {L.cvxpnpl_ransac_pnpl_lo_last_error().decode()}")
-    return Bt, Qt, cnt
+    return _lo_assemble_host(_lib.ransac_pnpl_lo_lib, "cvxpnpl_ransac_pnpl_lo", F, K, R, t, active, wrong, lambda L, ptr, act, Rh, th, Kh, Bt, Qt, cnt:
+                             L.cvxpnpl_ransac_pnpl_lo_assemble_host(F, act.shape[0], ptr(act), ptr(off_p), nP, ptr(off_l), nL, ptr(x), ptr(X), ptr(l2),
+                                                                    ptr(l3), ptr(Rh), ptr(th), ptr(Kh), int(Kh.ndim == 3), float(thresh_k), ptr(Bt),
+                                                                    ptr(Qt), ptr(cnt), int(n_threads)))
 
 
 def _check_pnpl_quality(quality, line_quality, pool_full, ps, ls, packed_p, packed_l, n_hyp):

@@ -31,7 +31,7 @@ def device_cmds(tree):
     spec.loader.exec_module(mod)
     cmds = {}
     for name in dir(mod):
-        if not name.endswith("compile_cmd"):
+        if not name.endswith(("compile_cmd", "_command")):  # (the thirteenth library on names its command ransac_*_command)
             continue
         cmd = getattr(mod, name)("OUT")
         flags = [c for i, c in enumerate(cmd) if c not in DROP and c != "-o" and cmd[i - 1] != "-o" and not c.endswith((".hip", ".cpp"))]
